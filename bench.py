@@ -11,7 +11,14 @@ DArray*DArray 16384^2 TFLOP/s (cfg4), and at N=8 mapreduce(abs2,+,f32)
 reduce stage-1 kernel, HBM-bound); `cpu_baseline` is the C/OpenMP oracle
 restatement (kind="port") timed on the host cores of the same box.
 
-Launch: python bench.py --gpus N --steps K --warmup W
+A plain run measures only the primary leg: set up, warm up, time the K
+steps, print the JSON line.  Every other leg (the `extra` legs, the
+dominant-kernel probe behind `roofline`, `cpu_baseline`) runs only with
+--full.  --dump-outputs DIR writes what the last timed step returned
+(the global sum) as DIR/sum.npy (float64, shape (1,)); the input is a
+fixed-seed philox fill, so two builds can be compared output for output.
+
+Launch: python bench.py --gpus N --steps K --warmup W [--full]
 (N>1 via torch.distributed.run, one rank per GPU; RANK/WORLD_SIZE from
 env; gloo is used for control barriers, RCCL via the C ABI for data).
 """
@@ -34,6 +41,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs, the dominant-kernel "
+                         "probe (roofline) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as "
+                         "DIR/sum.npy (float64)")
     ap.add_argument("--no-gemm", action="store_true")
     ap.add_argument("--elems", type=int, default=1 << 28,
                     help="per-GPU f64 elements for the sum/map legs")
@@ -89,27 +102,74 @@ def main():
     log("[bench] alloc + drand %d f64 elems/GPU" % n)
     D = dja.DArray((n * world,), "f64", (world,))
     D.rand_()
+    s = None
     for _ in range(W):
-        dja.dsum(D)
+        s = dja.dsum(D)
     # dominant-kernel duration via HIP events on the library stream,
     # probed OUTSIDE the timed region (events cost a few us per record)
-    e0, e1 = ev_pair()
     kern_ms = []
-    for _ in range(max(5, W)):
-        check(lib.da_event_record(e0))
-        dja.dsum(D)
-        check(lib.da_event_record(e1))
-        kern_ms.append(ev_ms(e0, e1))
+    if args.full:
+        e0, e1 = ev_pair()
+        for _ in range(max(5, W)):
+            check(lib.da_event_record(e0))
+            dja.dsum(D)
+            check(lib.da_event_record(e1))
+            kern_ms.append(ev_ms(e0, e1))
     barrier()
     t0 = time.perf_counter()
     for _ in range(K):
         s = dja.dsum(D)
     barrier()
     t_sum = max_over_ranks(time.perf_counter() - t0)
-    sum_gbs = world * n * 8.0 * K / t_sum / 1e9
+    sum_gbs = world * n * 8.0 * K / t_sum / 1e9 if K else 0.0
+    ms_per_step = t_sum / K * 1e3 if K else 0.0
+    log("[bench] sum: %.1f GB/s whole-job, %.3f ms/step, value=%r"
+        % (sum_gbs, ms_per_step, s))
+
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        if s is None:       # --steps 0 --warmup 0: nothing was computed
+            s = dja.dsum(D)
+        np.save(os.path.join(args.dump_outputs, "sum.npy"),
+                np.array([s], dtype=np.float64))
+
+    def report(roofline, cpu_baseline):
+        result = {
+            "metric": "sum(DArray) GB/s",
+            "value": sum_gbs,
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": "cfg2: sum(drand(Float64, 2^28)) per GPU, "
+                            "1-D block distribution",
+                "per_gpu_elems": n,
+                "global_elems": n * world,
+            },
+            "roofline": roofline,
+            "cpu_baseline": cpu_baseline,
+            "extra": extra,
+        }
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            td.destroy_process_group()
+
+    if not args.full:
+        D.close()
+        report(None, None)
+        return
+
     kms = sorted(kern_ms)[len(kern_ms) // 2]
-    log("[bench] sum: %.1f GB/s whole-job, %.3f ms/step (launch %.3f ms), "
-        "value=%r" % (sum_gbs, t_sum / K * 1e3, kms, s))
+    log("[bench] sum launch (HIP events, median): %.3f ms" % kms)
 
     # ---------------- cfg2: map!(sin, D, D) ----------------------------
     M = dja.DArray((n * world,), "f64", (world,))
@@ -310,33 +370,7 @@ def main():
         "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic,
     }
 
-    result = {
-        "metric": "sum(DArray) GB/s",
-        "value": sum_gbs,
-        "unit": "GB/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": t_sum / K * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": "cfg2: sum(drand(Float64, 2^28)) per GPU, "
-                        "1-D block distribution",
-            "per_gpu_elems": n,
-            "global_elems": n * world,
-        },
-        "roofline": roofline,
-        "cpu_baseline": cpu_baseline,
-        "extra": extra,
-    }
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        td.destroy_process_group()
+    report(roofline, cpu_baseline)
 
 
 if __name__ == "__main__":

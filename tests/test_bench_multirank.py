@@ -11,6 +11,52 @@ import pytest
 import torch.multiprocessing as mp
 
 
+def _plain_worker(rank, dump_dir, q, world):
+    """A plain run (no --full): primary leg only, --dump-outputs honoured."""
+    try:
+        os.environ["RANK"] = str(rank)
+        os.environ["WORLD_SIZE"] = str(world)
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(29100 + world)
+        import fakelib
+        fakelib.install()
+        n = 1 << 12
+        sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3",
+                    "--warmup", "1", "--elems", str(n),
+                    "--dump-outputs", dump_dir]
+        import io
+        import contextlib
+        import bench
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main()
+        if rank == 0:
+            import numpy as np
+            from oracle import philox
+            rec = json.loads(buf.getvalue().strip().splitlines()[-1])
+            assert rec["metric"] == "sum(DArray) GB/s"
+            assert rec["unit"] == "GB/s" and rec["dtype"] == "f64"
+            assert rec["higher_is_better"] is True
+            assert rec["steps"] == 3 and rec["n_gpus"] == world
+            assert rec["value"] > 0 and rec["ms_per_step"] > 0
+            # nothing but the headline leg ran
+            assert rec["extra"] == {}
+            assert rec["roofline"] is None and rec["cpu_baseline"] is None
+            assert os.listdir(dump_dir) == ["sum.npy"]
+            got = np.load(os.path.join(dump_dir, "sum.npy"))
+            assert got.dtype == np.float64 and got.shape == (1,)
+            # per-rank philox seed = 1234 + rank (DArray.rand_)
+            ref = sum(philox.fill_uniform_f64(n, seed=1234 + r).sum()
+                      for r in range(world))
+            assert abs(got[0] - ref) <= 1e-12 * abs(ref), (got[0], ref)
+        q.put((rank, True, None))
+    except SystemExit as e:
+        q.put((rank, e.code in (0, None), "SystemExit %r" % e.code))
+    except Exception:
+        import traceback
+        q.put((rank, False, traceback.format_exc()[-2000:]))
+
+
 def _bench_worker(rank, tmpfile, q, world):
     try:
         os.environ["RANK"] = str(rank)
@@ -21,7 +67,7 @@ def _bench_worker(rank, tmpfile, q, world):
         fakelib.install()
         sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2",
                     "--warmup", "1", "--elems", str(1 << 12),
-                    "--gemm-n", "96"]
+                    "--gemm-n", "96", "--full"]
         import io
         import contextlib
         import bench
@@ -56,11 +102,11 @@ def _bench_worker(rank, tmpfile, q, world):
         q.put((rank, False, traceback.format_exc()[-2000:]))
 
 
-def _spawn(tmp_path, world):
+def _spawn(tmp_path, world, worker=_bench_worker, arg="rdv"):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_bench_worker,
-                         args=(r, str(tmp_path / "rdv"), q, world))
+    procs = [ctx.Process(target=worker,
+                         args=(r, str(tmp_path / arg), q, world))
              for r in range(world)]
     for p in procs:
         p.start()
@@ -84,3 +130,8 @@ def test_bench_world4_cfg3_branch(tmp_path):
 @pytest.mark.timeout(600)
 def test_bench_world8_cfg5_branch(tmp_path):
     _spawn(tmp_path, 8)
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    _spawn(tmp_path, 2, worker=_plain_worker, arg="dump")
