@@ -63,6 +63,7 @@ _sigs = {
     "da_scale": ([ptr, f64, u64, i32], i32),
     "da_cast": ([ptr, i32, ptr, i32, u64], i32),
     "da_reduce": ([i32, i32, ptr, u64, i32, ptr], i32),
+    "da_count": ([i32, ptr, u64, i32, ctypes.POINTER(i64)], i32),
     "da_reduce_dims": ([i32, i32, ptr, u64, u64, u64, i32, ptr], i32),
     "da_transpose": ([ptr, ptr, u64, u64, i32], i32),
     "da_diag_scale": ([ptr, u64, u64, ptr, i32, i32], i32),
@@ -98,7 +99,16 @@ _sigs = {
     "da_bytes_in_use": ([], u64),
 }
 
-for name, (args, res) in _sigs.items():
+# debug-only host-side dispatcher selectors (declared in the header's debug
+# section; pure functions, callable without da_init or a GPU)
+_dbg_sigs = {
+    "dbg_reduce_dims_variant": ([u64, u64, u64], i32),
+    "dbg_gemm_path": ([i64, i64, i64], i32),
+}
+DIMS_VARIANTS = ("slices", "threads", "waves", "blocks")  # enum da_dims_variant
+GEMM_PATHS = ("naive", "mfma")                            # enum da_gemm_path_id
+
+for name, (args, res) in list(_sigs.items()) + list(_dbg_sigs.items()):
     fn = getattr(lib, name)
     fn.argtypes = args
     fn.restype = res

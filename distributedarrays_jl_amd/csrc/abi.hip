@@ -347,6 +347,12 @@ int da_reduce(int mapop, int redop, const void* src, uint64_t n, int dtype,
     return launch_reduce(mapop, redop, src, n, dtype, out, st().stream);
 }
 
+int da_count(int mapop, const void* src, uint64_t n, int dtype,
+             int64_t* out) {
+    DA_REQUIRE_INIT();
+    return launch_count(mapop, src, n, dtype, out, st().stream);
+}
+
 int da_reduce_dims(int mapop, int redop, const void* src, uint64_t inner,
                    uint64_t axis, uint64_t outer, int dtype, void* dst) {
     DA_REQUIRE_INIT();
@@ -423,6 +429,15 @@ int dbg_mfma_probe_f64(const void* A, const void* B, void* out_c,
 int dbg_mfma_probe_f32(const void* A, const void* B, void* out_raw) {
     DA_REQUIRE_INIT();
     return dbg_mfma_probe_f32_impl(A, B, out_raw, st().stream);
+}
+
+/* debug-only: host-side dispatcher selectors (no GPU, no da_init) */
+int dbg_reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer) {
+    return reduce_dims_variant(inner, axis, outer);
+}
+
+int dbg_gemm_path(int64_t m, int64_t n, int64_t k) {
+    return gemm_path(m, n, k);
 }
 
 /* ---- point-to-point --------------------------------------------------- */

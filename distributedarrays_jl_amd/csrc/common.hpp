@@ -123,6 +123,8 @@ int launch_cast(void* dst, int dst_dtype, const void* src, int src_dtype,
                 uint64_t n, hipStream_t s);
 int launch_reduce(int mapop, int redop, const void* src, uint64_t n,
                   int dtype, void* out_host, hipStream_t s);
+int launch_count(int mapop, const void* src, uint64_t n, int dtype,
+                 int64_t* out_host, hipStream_t s);
 int launch_reduce_dims(int mapop, int redop, const void* src,
                        uint64_t inner, uint64_t axis, uint64_t outer,
                        int dtype, void* dst, hipStream_t s);
@@ -138,6 +140,9 @@ int launch_gemm_f32(void* C, const void* A, const void* B,
                     int64_t m, int64_t n, int64_t k,
                     int64_t lda, int64_t ldb, int64_t ldc,
                     double alpha, double beta, hipStream_t s);
+// host-only dispatcher selectors (the launchers call these themselves)
+int reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer);
+int gemm_path(int64_t m, int64_t n, int64_t k);
 int dbg_mfma_probe_impl(const void* A, const void* B, void* out_c,
                         void* out_raw, hipStream_t s);
 int dbg_mfma_probe_f32_impl(const void* A, const void* B, void* out_raw,

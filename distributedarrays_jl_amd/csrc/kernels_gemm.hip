@@ -695,6 +695,13 @@ __global__ void scale_c_t(T* __restrict__ C, int64_t m, int64_t n,
     C[j * ldc + i] = (beta == (T)0) ? (T)0 : beta * C[j * ldc + i];
 }
 
+// Host-only MFMA-vs-naive choice shared by launch_gemm_f64/f32 (exported
+// as dbg_gemm_path): the MFMA kernels need whole 128x128x16 tiles.
+int gemm_path(int64_t m, int64_t n, int64_t k) {
+    return (m % BM == 0 && n % BN == 0 && k % BK == 0) ? DA_GEMM_MFMA
+                                                       : DA_GEMM_NAIVE;
+}
+
 int launch_gemm_f32(void* Cv, const void* Av, const void* Bv,
                     int64_t m, int64_t n, int64_t k,
                     int64_t lda, int64_t ldb, int64_t ldc,
@@ -712,7 +719,7 @@ int launch_gemm_f32(void* Cv, const void* Av, const void* Bv,
         DA_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    if (m % BM == 0 && n % BN == 0 && k % BK == 0) {
+    if (gemm_path(m, n, k) == DA_GEMM_MFMA) {
         dim3 g(m / BM, n / BN);
         hipLaunchKernelGGL(gemm_f32_mfma_v3, g, dim3(512), 0, s,
                            A, B, C, m, n, k, lda, ldb, ldc, al, be);
@@ -754,7 +761,7 @@ int launch_gemm_f64(void* Cv, const void* Av, const void* Bv,
         DA_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    if (m % BM == 0 && n % BN == 0 && k % BK == 0) {
+    if (gemm_path(m, n, k) == DA_GEMM_MFMA) {
         dim3 g(m / BM, n / BN);
         static int variant = -1, bk = -1;
         if (variant < 0) {

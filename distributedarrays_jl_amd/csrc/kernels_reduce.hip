@@ -306,6 +306,78 @@ static int do_reduce(int mapop, int redop, const T* src, uint64_t n,
     return 0;
 }
 
+// Exact predicate count: the 0/1 predicate of a T source is accumulated
+// in int64_t (a float accumulator rounds above 2^24 / 2^53), then the
+// block partials fold through the ordinary i64 stage 2.
+template <typename T>
+__device__ __forceinline__ int64_t predf(int mapop, T x) {
+    switch (mapop) {
+    case DA_REDF_ISNAN: return x != x ? 1 : 0;
+    case DA_REDF_ISFINITE: return isfinite((double)x) ? 1 : 0;
+    }
+    return x != (T)0 ? 1 : 0;   // DA_REDF_NONZERO
+}
+template <>
+__device__ __forceinline__ int64_t predf<int64_t>(int mapop, int64_t x) {
+    return mapf(mapop, x);
+}
+
+template <typename T>
+__global__ void count_stage1(int mapop, const T* __restrict__ src,
+                             uint64_t n, int64_t* __restrict__ partials) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    int64_t acc = 0;
+    using V = T __attribute__((ext_vector_type(2)));
+    uint64_t nv = n / 2;
+    const V* sv = reinterpret_cast<const V*>(src);
+    for (uint64_t j = i; j < nv; j += stride) {
+        V v = sv[j];
+        acc += predf<T>(mapop, (T)v.x) + predf<T>(mapop, (T)v.y);
+    }
+    for (uint64_t j = 2 * nv + i; j < n; j += stride)
+        acc += predf<T>(mapop, src[j]);
+    acc = block_reduce(DA_RED_ADD, acc);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+template <typename T>
+static int do_count(int mapop, const T* src, uint64_t n, int64_t* out_host,
+                    hipStream_t s) {
+    int g = reduce_grid((n / 2 + RTPB - 1) / RTPB);
+    int rc = ensure_partials((RMAXB + 1) * sizeof(double));
+    if (rc) return rc;
+    int64_t* parts = (int64_t*)st().partials;
+    int64_t* dout = parts + RMAXB;
+    hipLaunchKernelGGL(count_stage1<T>, dim3(g), dim3(RTPB), 0, s,
+                       mapop, src, n, parts);
+    DA_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(reduce_stage2<int64_t>, dim3(1), dim3(RTPB), 0, s,
+                       (int)DA_RED_ADD, parts, g, dout);
+    DA_CHECK_HIP(hipGetLastError());
+    DA_CHECK_HIP(hipMemcpyAsync(out_host, dout, sizeof(int64_t),
+                                hipMemcpyDeviceToHost, s));
+    DA_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int launch_count(int mapop, const void* src, uint64_t n, int dtype,
+                 int64_t* out_host, hipStream_t s) {
+    if (mapop < DA_REDF_ISNAN || mapop > DA_REDF_NONZERO)
+        return set_err(-3, "da_count: mapop %d is not a predicate", mapop);
+    if (!out_host) return set_err(-3, "da_count: null out");
+    if (dtype != DA_F64 && dtype != DA_F32 && dtype != DA_I64)
+        return set_err(-3, "da_count: bad dtype %d", dtype);
+    if (n == 0) { *out_host = 0; return 0; }
+    switch (dtype) {
+    case DA_F64: return do_count<double>(mapop, (const double*)src, n,
+                                         out_host, s);
+    case DA_F32: return do_count<float>(mapop, (const float*)src, n,
+                                        out_host, s);
+    }
+    return do_count<int64_t>(mapop, (const int64_t*)src, n, out_host, s);
+}
+
 // ---- dims-reduction (mapreduce.jl:42-94: per-chunk mapreduce(dims=..))
 // The chunk is viewed column-major as (inner, axis, outer):
 // src[i + a*inner + o*inner*axis] -> dst[i + o*inner], reduced over a.
@@ -424,6 +496,19 @@ __global__ void reduce_dims_slices2(int redop, const T* __restrict__ partials,
     }
 }
 
+// Host-only variant choice of the dims-reduce dispatcher (exported as
+// dbg_reduce_dims_variant so tests can pin which kernel a shape reaches).
+int reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer) {
+    uint64_t total = inner * outer;
+    if (total < 262144 && inner >= 64 && axis >= 64 && outer <= 64)
+        return DA_DIMS_SLICES;   // few outputs, large inner, long axis
+    if (total >= 262144 && inner >= 64)
+        return DA_DIMS_THREADS;  // plenty of outputs, coalesced across inner
+    if (inner < 64 && axis >= 64 && total >= 16384)
+        return DA_DIMS_WAVES;    // inner tiny: lanes stride the axis
+    return DA_DIMS_BLOCKS;       // few outputs / long axis
+}
+
 template <typename T, int MOP, int ROP>
 static int do_reduce_dims_t(int mapop, int redop, const T* src,
                             uint64_t inner, uint64_t axis, uint64_t outer,
@@ -432,7 +517,8 @@ static int do_reduce_dims_t(int mapop, int redop, const T* src,
     if (total == 0) return 0;
     // axis == 0 still runs: the loop body never executes and dst gets
     // the fold identity.
-    if (total < 262144 && inner >= 64 && axis >= 64 && outer <= 64) {
+    const int variant = reduce_dims_variant(inner, axis, outer);
+    if (variant == DA_DIMS_SLICES) {
         // fill ~2048 workgroups: (inner/256 row tiles) x nb slices
         uint64_t row_tiles = (inner + RTPB - 1) / RTPB;
         int nb = (int)(2048 / row_tiles);
@@ -454,14 +540,14 @@ static int do_reduce_dims_t(int mapop, int redop, const T* src,
         DA_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    if (total >= 262144 && inner >= 64) {
+    if (variant == DA_DIMS_THREADS) {
         // plenty of outputs, coalesced across inner: thread-per-output
         uint64_t want = (total + RTPB - 1) / RTPB;
         int g = (int)(want < 1 ? 1 : (want > 8192 ? 8192 : want));
         hipLaunchKernelGGL((reduce_dims_threads<T, MOP, ROP>), dim3(g),
                            dim3(RTPB), 0,
                            s, mapop, redop, src, inner, axis, outer, dst);
-    } else if (inner < 64 && axis >= 64 && total >= 16384) {
+    } else if (variant == DA_DIMS_WAVES) {
         // inner tiny (reduce over leading dim): wave-per-output, lanes
         // stride the axis (coalesced along the axis)
         uint64_t want = (total * 64 + RTPB - 1) / RTPB;

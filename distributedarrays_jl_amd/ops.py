@@ -223,6 +223,7 @@ def map_localparts_(f, d):
 # ------------------------------------------------------------ reductions
 _CTYPE = {"f64": ctypes.c_double, "f32": ctypes.c_float,
           "i64": ctypes.c_int64}
+_PREDICATES = ("isnan", "isfinite", "nonzero")
 
 
 def _local_reduce(f, op, d):
@@ -275,8 +276,18 @@ def dmean(d):
 
 def dcount(pred, d):
     """count(f, A) — mapreduce.jl:115-122 (pred in {nonzero, isnan,
-    isfinite})."""
-    return int(mapreduce(pred, "add", d))
+    isfinite}).  Exact for every dtype and size: the predicate is
+    counted in a 64-bit integer on the device (da_count) and folded
+    across ranks as i64 — a float accumulator rounds above 2^24."""
+    if pred not in _PREDICATES:
+        raise DArrayError("dcount: %r is not a predicate" % (pred,))
+    out = ctypes.c_int64()
+    check(lib.da_count(RED_FS[pred], d._ptr(), d.lnumel, DTYPES[d.dtype],
+                       ctypes.byref(out)))
+    if d.nranks > 1:
+        check(lib.da_allreduce(ctypes.byref(out), 1, DTYPES["i64"],
+                               RED_OPS["add"]))
+    return int(out.value)
 
 
 def dall(pred, d):

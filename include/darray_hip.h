@@ -159,6 +159,13 @@ int da_cast(void* dst, int dst_dtype, const void* src, int src_dtype,
  * n == 0 returns the fold identity. */
 int da_reduce(int mapop, int redop, const void* src, uint64_t n, int dtype,
               void* out);
+/* Exact predicate count (count(f, A), mapreduce.jl:115-122): mapop must be
+ * a predicate (DA_REDF_ISNAN / ISFINITE / NONZERO).  The 0/1 values are
+ * accumulated in a 64-bit integer on the device whatever the source dtype,
+ * so *out is exact for every n (a float accumulator rounds above 2^24).
+ * Fold across ranks with da_allreduce(out, 1, DA_I64, DA_RED_ADD). */
+int da_count(int mapop, const void* src, uint64_t n, int dtype,
+             int64_t* out);
 /* Per-chunk dims-reduction (src/mapreduce.jl:42-94, mapreducedim_within):
  * chunk viewed column-major as (inner, axis, outer); dst gets
  * inner*outer elements reduced over axis (identity when axis==0). */
@@ -172,7 +179,16 @@ int da_allreduce(void* inout, int count, int dtype, int redop);
 /* ---- dense linear algebra -------------------------------------------- */
 /* Local C = alpha*A*B + beta*C, COLUMN-major f64 (Julia layout), MFMA-
  * tiled for gfx950 — the localpart(A)*B_jk of src/linalg.jl:224.
- * lda/ldb/ldc are element leading dimensions. */
+ * lda/ldb/ldc are element leading dimensions (>= rows; padded panels and
+ * sub-matrix pointers into a larger parent are allowed).
+ * Alignment (da_gemm_f64 / da_gemm_f32 / da_gemm_i64): the MFMA kernels
+ * stage operands with 16-byte vector loads, so A, B and C must be 16-byte
+ * aligned and lda/ldb/ldc multiples of 16 bytes (2 f64 / 4 f32 elements)
+ * whenever m%128 == n%128 == k%16 == 0; chunks from da_alloc with
+ * 16-element-aligned leading dimensions and offsets always qualify.  The
+ * naive path (any other shape, and da_gemm_i64) needs element alignment
+ * only.  beta == 0 overwrites C without reading it (NaN in C is ignored);
+ * alpha == 0 or k == 0 yields beta*C without reading A or B. */
 int da_gemm_f64(void* C, const void* A, const void* B,
                 int64_t m, int64_t n, int64_t k,
                 int64_t lda, int64_t ldb, int64_t ldc,
@@ -226,6 +242,17 @@ int da_event_create(void** ev);
 int da_event_record(void* ev);
 int da_event_elapsed(void* ev_start, void* ev_stop, float* ms);
 int da_event_destroy(void* ev);
+
+/* ---- debug: host-only dispatcher selectors (no GPU work, callable
+ *      before da_init).  The launchers call the same functions, so a test
+ *      can assert which kernel a shape reaches before launching it. ------ */
+enum da_dims_variant { DA_DIMS_SLICES = 0, DA_DIMS_THREADS, DA_DIMS_WAVES,
+                       DA_DIMS_BLOCKS };
+enum da_gemm_path_id { DA_GEMM_NAIVE = 0, DA_GEMM_MFMA = 1 };
+/* kernel family da_reduce_dims picks for a (inner, axis, outer) view */
+int dbg_reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer);
+/* MFMA or naive kernel for da_gemm_f64/f32 at (m, n, k), k > 0, alpha != 0 */
+int dbg_gemm_path(int64_t m, int64_t n, int64_t k);
 
 /* ---- introspection / errors ------------------------------------------ */
 const char* da_errstr(int code);

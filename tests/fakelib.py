@@ -254,6 +254,14 @@ class FakeLib:
             float(val) if int(dtype) != 2 else int(val)
         return 0
 
+    def da_count(self, mapop, src, n, dtype, out):
+        name = _REDF_NAMES[int(mapop)]
+        assert name in ("isnan", "isfinite", "nonzero"), name
+        chunk = _tv(src, n, _NPDT[int(dtype)])
+        val = int(np.count_nonzero(oops.MAPRED_FS[name](chunk)))
+        ctypes.cast(out, ctypes.POINTER(ctypes.c_int64))[0] = val
+        return 0
+
     def da_reduce_dims(self, mapop, redop, src, inner, axis, outer,
                        dtype, dst):
         dt = _NPDT[int(dtype)]

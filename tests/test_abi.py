@@ -43,6 +43,54 @@ def test_ffi_covers_header():
                            % (syms - bound, bound - syms))
 
 
+def header_debug_symbols():
+    txt = open(HDR).read()
+    return sorted(set(re.findall(r"^int\s+(dbg_\w+)\s*\(", txt, re.M)))
+
+
+def test_debug_selectors_header_ffi_exported(built):
+    from distributedarrays_jl_amd import _ffi
+    syms = set(header_debug_symbols())
+    assert syms == {"dbg_reduce_dims_variant", "dbg_gemm_path"}
+    assert syms == set(_ffi._dbg_sigs)
+    missing = [s for s in syms if not hasattr(built, s)]
+    assert not missing, "not exported: %r" % missing
+
+
+def test_selector_enums_agree_with_header():
+    from distributedarrays_jl_amd import _ffi
+    txt = open(HDR).read()
+    m = re.search(r"enum da_dims_variant \{(.*?)\};", txt, re.S)
+    names = re.findall(r"DA_DIMS_(\w+)", m.group(1))
+    assert tuple(n.lower() for n in names) == _ffi.DIMS_VARIANTS
+    m = re.search(r"enum da_gemm_path_id \{(.*?)\};", txt, re.S)
+    names = re.findall(r"DA_GEMM_(\w+)", m.group(1))
+    assert tuple(n.lower() for n in names) == _ffi.GEMM_PATHS
+
+
+def test_selectors_are_pure_host_functions():
+    """No da_init, no GPU: the selectors answer from the shape alone, at
+    each side of every dispatcher threshold."""
+    from distributedarrays_jl_amd import _ffi
+    var = lambda *s: _ffi.DIMS_VARIANTS[_ffi.lib.dbg_reduce_dims_variant(*s)]
+    assert var(64, 64, 1) == "slices"
+    assert var(64, 63, 1) == "blocks"          # axis under a wave
+    assert var(64, 64, 65) == "blocks"         # outer > 64
+    assert var(63, 64, 1) == "blocks"          # inner < 64, too few outputs
+    assert var(64, 3, 4096) == "threads"       # 262144 outputs
+    assert var(64, 3, 4095) == "blocks"        # 262080 outputs, axis < 64
+    assert var(1, 64, 16384) == "waves"
+    assert var(1, 64, 16383) == "blocks"
+    assert var(1, 63, 16384) == "blocks"
+    assert var(1, 1, 1) == "blocks"
+    path = lambda *s: _ffi.GEMM_PATHS[_ffi.lib.dbg_gemm_path(*s)]
+    assert path(128, 128, 16) == "mfma"
+    assert path(129, 128, 16) == "naive"
+    assert path(128, 127, 16) == "naive"
+    assert path(128, 128, 17) == "naive"
+    assert path(1152, 128, 32) == "mfma"
+
+
 def test_opcode_tables_agree_with_header():
     from distributedarrays_jl_amd import _opcodes
     txt = open(HDR).read()
