@@ -423,12 +423,12 @@ int da_diag_scale(void* a, uint64_t m, uint64_t n, const void* diag,
 int dbg_mfma_probe_f64(const void* A, const void* B, void* out_c,
                        void* out_raw) {
     DA_REQUIRE_INIT();
-    return dbg_mfma_probe_impl(A, B, out_c, out_raw, st().stream);
+    return dbg_mfma_probe_impl(DA_F64, A, B, out_c, out_raw, st().stream);
 }
 
 int dbg_mfma_probe_f32(const void* A, const void* B, void* out_raw) {
     DA_REQUIRE_INIT();
-    return dbg_mfma_probe_f32_impl(A, B, out_raw, st().stream);
+    return dbg_mfma_probe_impl(DA_F32, A, B, nullptr, out_raw, st().stream);
 }
 
 /* debug-only: host-side dispatcher selectors (no GPU, no da_init) */

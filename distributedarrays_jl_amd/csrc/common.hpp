@@ -143,9 +143,8 @@ int launch_gemm_f32(void* C, const void* A, const void* B,
 // host-only dispatcher selectors (the launchers call these themselves)
 int reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer);
 int gemm_path(int64_t m, int64_t n, int64_t k);
-int dbg_mfma_probe_impl(const void* A, const void* B, void* out_c,
-                        void* out_raw, hipStream_t s);
-int dbg_mfma_probe_f32_impl(const void* A, const void* B, void* out_raw,
-                            hipStream_t s);
+// dtype DA_F64 or DA_F32; out_c may be null (only out_raw is written)
+int dbg_mfma_probe_impl(int dtype, const void* A, const void* B,
+                        void* out_c, void* out_raw, hipStream_t s);
 
 } // namespace da

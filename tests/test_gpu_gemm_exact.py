@@ -20,6 +20,7 @@ MFMA_SHAPES = [
     (128, 128, 32),
     (384, 384, 48),     # 9 workgroups
     (640, 896, 16),     # 35 workgroups, single k-tile
+    (640, 896, 32),     # 35 workgroups, two k-tiles
     (128, 1152, 32),    # grid 1x9
     (1152, 128, 32),    # grid 9x1
     (256, 128, 1024),   # deep k
@@ -52,6 +53,26 @@ def test_mfma_shapes_exact(lib, shape, dt):
 def test_mfma_shapes_real_inputs_in_bound(lib, shape, dt):
     assert kc.gemm_path(lib, *shape) == "mfma"
     kc.gemm_real_in_bound(lib, dt, *shape)
+
+
+TILE_SHAPES = [(128, 128, 16), (384, 384, 48), (640, 896, 32)]
+
+
+def test_mfma_plain_padded_beta0(lib):
+    """One, 9 and 35 workgroups through the tile kernel, both float dtypes:
+    plain, padded with accumulation, and beta = 0 over a NaN C (C is never
+    read).  One test, not a parametrised one: it is the check set that the
+    former DA_GEMM_V=3 variant child ran, now in the default process."""
+    for shape in TILE_SHAPES:
+        m, n, k = shape
+        assert kc.gemm_path(lib, *shape) == "mfma"
+        for dt in FLOATS:
+            kc.gemm_exact(lib, dt, m, n, k)
+            kc.gemm_exact(lib, dt, m, n, k, alpha=1, beta=-2,
+                          layout=kc.padded())
+            kc.gemm_exact(lib, dt, m, n, k, beta=0,
+                          c_block=kc.nan_block(m, n, dt))
+        kc.gemm_real_in_bound(lib, "f64", m, n, k)
 
 
 @pytest.mark.parametrize("dt", FLOATS)

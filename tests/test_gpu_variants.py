@@ -1,5 +1,5 @@
 """Every env-gated kernel variant, inside the suite.  The switches
-(DA_GEMM_V, DA_RED_FUSED, DA_RV4, DA_RBLOCKS, ...) are read once per
+(DA_RED_FUSED, DA_RV4, DA_RBLOCKS, DA_NT, ...) are read once per
 process, so each variant runs tests/variant_child.py in a fresh child with
 the switch in ITS environment; this process's environment and program are
 never changed.  Children run strictly one at a time.  If one dies by a

@@ -4,7 +4,7 @@ parent put in the environment.  The kernel-variant switches are read once
 per process, so every variant gets a fresh interpreter; the parent starts
 the children strictly one at a time and stops at the first one that dies.
 
-    python tests/variant_child.py {gemm|reduce|small}
+    python tests/variant_child.py {reduce|small}
 
 VARIANTS is the single table of env-gated variants and the set each runs.
 """
@@ -15,11 +15,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # (environment, check set)
 VARIANTS = [
-    ({"DA_GEMM_V": "1"}, "gemm"),
-    ({"DA_GEMM_V": "2"}, "gemm"),
-    ({"DA_GEMM_V": "3"}, "gemm"),
-    ({"DA_GEMM_V": "5"}, "gemm"),
-    ({"DA_GEMM_V": "2", "DA_GEMM_BK": "32"}, "gemm"),
     ({"DA_RED_FUSED": "1"}, "reduce"),
     ({"DA_RV4": "1"}, "reduce"),
     ({"DA_RBLOCKS": "1"}, "reduce"),
@@ -35,23 +30,6 @@ VARIANTS = [
 
 def variant_id(env):
     return ",".join("%s=%s" % kv for kv in sorted(env.items()))
-
-
-def run_gemm(dja, lib):
-    """f64 MFMA variants (v1, v2<16>, v2<32>, v3, v5): single k-tile, 9 and
-    35 workgroups; (384,384,48) has k % 32 != 0, so DA_GEMM_BK=32 falls
-    back to v2<16> there.  Plain, padded, and beta = 0 over a NaN C."""
-    import kernel_checks as kc
-    for shape in [(128, 128, 16), (384, 384, 48), (640, 896, 32)]:
-        m, n, k = shape
-        assert kc.gemm_path(lib, *shape) == "mfma"
-        for dt in ("f64", "f32"):
-            kc.gemm_exact(lib, dt, m, n, k)
-            kc.gemm_exact(lib, dt, m, n, k, alpha=1, beta=-2,
-                          layout=kc.padded())
-            kc.gemm_exact(lib, dt, m, n, k, beta=0,
-                          c_block=kc.nan_block(m, n, dt))
-        kc.gemm_real_in_bound(lib, "f64", m, n, k)
 
 
 def run_reduce(dja, lib):
@@ -101,7 +79,7 @@ def run_small(dja, lib):
         h.close()
 
 
-SETS = {"gemm": run_gemm, "reduce": run_reduce, "small": run_small}
+SETS = {"reduce": run_reduce, "small": run_small}
 
 
 def main(argv):
