@@ -20,7 +20,7 @@ from . import comm, geometry, plan, spmd, expr
 from .darray import (DArray, dzeros, dones, dfill, drand, drandn,
                      distribute, localpart, localindices, d_closeall,
                      bytes_in_use, ddata, dgather, locate, allowscalar,
-                     dfromfunction)
+                     dfromfunction, SubDArray, dview)
 from .ops import (map_, dmap, map2_, elementwise, map2_scalar_, elementwise_scalar, broadcast_fma, axpy_,
                   add_, scale_, mapreduce, dsum, dprod, dmaximum, dminimum,
                   dextrema, dmean, dcount, dall, dany, ddot, dnorm, dmatmul, dreduce_dims,
@@ -30,7 +30,8 @@ from .ops import (map_, dmap, map2_, elementwise, map2_scalar_, elementwise_scal
                   dmapslices, dppeval, dcast, dreshape,
                   map2_general,
                   broadcast_fma_general, dsort, dtranspose, ddiag_lmul, ddiag_rmul,
-                  dgetindex, dmul_)
+                  dgetindex, dmul_, gather_sel, dgetindex_sel, dsub,
+                  dsetindex_)
 
 __all__ = [
     "DArray", "DArrayError", "comm", "geometry", "plan", "spmd", "expr",
@@ -47,4 +48,6 @@ __all__ = [
     "map2_general",
     "gather_box", "map_general", "broadcast_fma_general", "dsort",
     "dtranspose", "ddiag_lmul", "ddiag_rmul", "dgetindex", "dmul_",
+    "SubDArray", "dview", "gather_sel", "dgetindex_sel", "dsub",
+    "dsetindex_",
 ]

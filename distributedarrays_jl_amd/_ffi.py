@@ -48,6 +48,10 @@ _sigs = {
     "da_d2h": ([ptr, ptr, u64], i32),
     "da_d2d": ([ptr, ptr, u64], i32),
     "da_copy2d": ([ptr, u64, ptr, u64, u64, u64], i32),
+    "da_copy_nd_plan": ([ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32,
+                         i32], i32),
+    "da_copy_nd": ([ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr,
+                    i32, i32], i32),
     "da_fill": ([ptr, f64, u64, i32], i32),
     "da_rand": ([ptr, u64, i32, u64, i32, u64], i32),
     "da_map": ([i32, ptr, ptr, u64, i32], i32),
@@ -107,6 +111,8 @@ _dbg_sigs = {
 }
 DIMS_VARIANTS = ("slices", "threads", "waves", "blocks")  # enum da_dims_variant
 GEMM_PATHS = ("naive", "mfma")                            # enum da_gemm_path_id
+COPY_FAMILIES = ("runs", "general")                       # enum da_copy_family
+COPY_MAXND = 6                                            # DA_COPY_MAXND
 
 for name, (args, res) in list(_sigs.items()) + list(_dbg_sigs.items()):
     fn = getattr(lib, name)

@@ -127,6 +127,7 @@ int da_shutdown(void) {
     if (st().comm) { ncclCommDestroy(st().comm); st().comm = nullptr; }
     if (st().scratch) { hipFree(st().scratch); st().scratch = nullptr; }
     if (st().partials) { hipFree(st().partials); st().partials = nullptr; }
+    (void)copy_nd_release();
     st().scratch_bytes = st().partials_bytes = 0;
     {
         std::lock_guard<std::mutex> g(st().mem_mtx);
@@ -264,6 +265,29 @@ int da_copy2d(void* dst, uint64_t dpitch, const void* src, uint64_t spitch,
     DA_CHECK_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height,
                                   hipMemcpyDeviceToDevice, st().stream));
     return 0;
+}
+
+int da_copy_nd_plan(const uint64_t* dst_shape, const int64_t* dst_start,
+                    const int64_t* dst_step, const int64_t* const* dst_idx,
+                    const uint64_t* src_shape, const int64_t* src_start,
+                    const int64_t* src_step, const int64_t* const* src_idx,
+                    const uint64_t* count, int nd, int dtype) {
+    /* host-only: no da_init needed */
+    return copy_nd_plan(dst_shape, dst_start, dst_step, dst_idx,
+                        src_shape, src_start, src_step, src_idx,
+                        count, nd, dtype);
+}
+
+int da_copy_nd(void* dst, const uint64_t* dst_shape, const int64_t* dst_start,
+               const int64_t* dst_step, const int64_t* const* dst_idx,
+               const void* src, const uint64_t* src_shape,
+               const int64_t* src_start, const int64_t* src_step,
+               const int64_t* const* src_idx,
+               const uint64_t* count, int nd, int dtype) {
+    DA_REQUIRE_INIT();
+    return launch_copy_nd(dst, dst_shape, dst_start, dst_step, dst_idx,
+                          src, src_shape, src_start, src_step, src_idx,
+                          count, nd, dtype, st().stream);
 }
 
 /* ---- constructors / elementwise / reductions ------------------------- */

@@ -140,6 +140,21 @@ int launch_gemm_f32(void* C, const void* A, const void* B,
                     int64_t m, int64_t n, int64_t k,
                     int64_t lda, int64_t ldb, int64_t ldc,
                     double alpha, double beta, hipStream_t s);
+// N-D selection copy (kernels_index.hip).  copy_nd_plan is the host-only
+// validator / family selector; launch_copy_nd calls it before launching.
+int copy_nd_plan(const uint64_t* dst_shape, const int64_t* dst_start,
+                 const int64_t* dst_step, const int64_t* const* dst_idx,
+                 const uint64_t* src_shape, const int64_t* src_start,
+                 const int64_t* src_step, const int64_t* const* src_idx,
+                 const uint64_t* count, int nd, int dtype);
+int launch_copy_nd(void* dst, const uint64_t* dst_shape,
+                   const int64_t* dst_start, const int64_t* dst_step,
+                   const int64_t* const* dst_idx,
+                   const void* src, const uint64_t* src_shape,
+                   const int64_t* src_start, const int64_t* src_step,
+                   const int64_t* const* src_idx,
+                   const uint64_t* count, int nd, int dtype, hipStream_t s);
+int copy_nd_release();   // frees the index-vector staging (da_shutdown)
 // host-only dispatcher selectors (the launchers call these themselves)
 int reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer);
 int gemm_path(int64_t m, int64_t n, int64_t k);

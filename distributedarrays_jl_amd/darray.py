@@ -349,12 +349,16 @@ class DArray:
         return value
 
     def __getitem__(self, key):
-        """D[i, j] / D[a:b, c:d] — the reference's scalar and
-        contiguous-range getindex (darray.jl:637-820, within this
-        build's range scope; strided/fancy indexing is out of scope).
+        """D[i, j] / D[a:b, c:d] / D[::2, [5, 0, 2]] — the reference's
+        scalar, range, stepped-range and index-vector getindex
+        (darray.jl:637-820, :661), 0-based with half-open Python
+        slices.  Several subscripts combine as an OUTER PRODUCT, as in
+        Julia: M[[0,2],[1,3]] is m[np.ix_([0,2],[1,3])], not numpy's
+        zipped fancy indexing.
         Collective at nranks>1: every rank must index identically.
         Scalars gate on allowscalar; ranges gather via the makelocal
-        box path and return a numpy array on every rank."""
+        box path, stepped slices and lists via the selection gather;
+        both return a numpy array on every rank."""
         if not isinstance(key, tuple):
             key = (key,)
         if len(key) != self.ndims:
@@ -362,6 +366,14 @@ class DArray:
                 "indexing needs %d subscripts" % self.ndims)
         if all(isinstance(k, (int, np.integer)) for k in key):
             return self.getindex(*(int(k) for k in key))
+        if _has_strided(key):
+            # stepped slices / integer lists (darray.jl:661): subscripts
+            # combine as an OUTER PRODUCT, as in Julia — M[[0,2],[1,3]] is
+            # m[np.ix_([0,2],[1,3])], not numpy's zipped fancy indexing
+            from . import ops, plan
+            sel, squeeze = plan.sel_normalize(key, self.dims)
+            out = ops.dgetindex_sel(self, sel)
+            return out.squeeze(axis=squeeze) if squeeze else out
         from . import ops
         ranges = []
         for d, k in enumerate(key):
@@ -382,13 +394,19 @@ class DArray:
         return out.squeeze(axis=squeeze) if squeeze else out
 
     def __setitem__(self, key, value):
-        """Scalar D[i, j] = v (darray.jl:700ff); collective."""
+        """D[i, j] = v (darray.jl:700ff) and D[sel...] = v
+        (copyto!(dest::SubOrDArray, src), darray.jl:679-687); collective.
+        With ranges, stepped slices or integer lists among the subscripts
+        (outer product, as in Julia) v is a scalar, a numpy array, a
+        DArray or a SubDArray of the selection's shape; a repeated entry
+        in an index list raises DArrayError."""
         if not isinstance(key, tuple):
             key = (key,)
         if not all(isinstance(k, (int, np.integer)) for k in key):
-            raise _ffi.DArrayError(
-                "only scalar setindex is supported (range assignment "
-                "is the out-of-scope SubDArray machinery)")
+            from . import ops, plan
+            sel, squeeze = plan.sel_normalize(key, self.dims)
+            ops.dsetindex_(self, sel, value, squeeze)
+            return
         self.setindex(value, *(int(k) for k in key))
 
     def __eq__(self, other):
@@ -445,6 +463,110 @@ class DArray:
         return ("DArray(dims=%r, dist=%r, dtype=%s, rank=%d/%d, lshape=%r)"
                 % (self.dims, self.dist, self.dtype, self.rank, self.nranks,
                    self.lshape))
+
+
+def _has_strided(key):
+    """True when a subscript tuple needs the selection path: a slice with
+    a step other than None/1, or an integer list / array."""
+    for k in key:
+        if isinstance(k, slice):
+            if k.step not in (None, 1):
+                return True
+        elif isinstance(k, (list, tuple, range, np.ndarray)):
+            return True
+    return False
+
+
+class SubDArray:
+    """Lazy view of a DArray (SubDArray = SubArray{..,DArray},
+    darray.jl:57-58): holds the parent and a selection, owns no device
+    memory.  Built by dview(); subscripts are 0-based ints, slices (any
+    step) and integer lists, combined as an OUTER PRODUCT as in Julia
+    (dview(M, [0,2], [1,3]) selects m[np.ix_([0,2],[1,3])]).  Int
+    subscripts drop their dimension from .shape."""
+
+    def __init__(self, parent, sel, squeeze):
+        self.parent = parent
+        self.sel = sel
+        self.squeeze = tuple(squeeze)
+
+    @property
+    def shape(self):
+        from . import plan
+        return tuple(n for d, n in enumerate(plan.sel_shape(self.sel))
+                     if d not in self.squeeze)
+
+    @property
+    def dims(self):
+        return self.shape
+
+    @property
+    def dtype(self):
+        return self.parent.dtype
+
+    def collect(self):
+        """Array(s) (darray.jl:584-602, :798-820): the selected elements
+        as a numpy array on every rank; collective."""
+        from . import ops
+        out = ops.dgetindex_sel(self.parent, self.sel)
+        return out.squeeze(axis=self.squeeze) if self.squeeze else out
+
+    def copy(self):
+        """DArray(s) (darray.jl:604-610): materialise the view as a new
+        DArray; collective."""
+        from . import ops
+        return ops.dsub(self.parent, self.sel, self.squeeze)
+
+    def __getitem__(self, key):
+        """A view of this view (composed selection; stays lazy)."""
+        from . import plan
+        if not isinstance(key, tuple):
+            key = (key,)
+        inner, sq = plan.sel_normalize(key, self.shape)
+        nd = len(self.sel)
+        kept = [d for d in range(nd) if d not in self.squeeze]
+        squeeze = self.squeeze + tuple(kept[d] for d in sq)
+        sel = plan.compose(self.sel,
+                           plan.sel_expand(inner, nd, self.squeeze))
+        return SubDArray(self.parent, sel, squeeze)
+
+    def __setitem__(self, key, value):
+        """s[...] = v assigns through to the parent; collective."""
+        from . import ops
+        sub = self[key]
+        ops.dsetindex_(sub.parent, sub.sel, value, sub.squeeze)
+
+    def __eq__(self, other):
+        """== against an ndarray, a DArray or a SubDArray
+        (darray.jl:415-445): materialises the view(s) and compares with
+        DArray.__eq__; collective."""
+        if not isinstance(other, (np.ndarray, DArray, SubDArray)):
+            return NotImplemented
+        mine = self.copy()
+        theirs = other.copy() if isinstance(other, SubDArray) else other
+        try:
+            return mine == theirs
+        finally:
+            mine.close()
+            if theirs is not other:
+                theirs.close()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "SubDArray(shape=%r, parent=%r)" % (self.shape, self.parent)
+
+
+def dview(d, *subs):
+    """view(d, I...) (darray.jl:57-58, :661) -> SubDArray: a lazy view
+    selecting ints, slices (any step, negative too) and integer lists per
+    dimension, 0-based.  Several subscripts combine as an OUTER PRODUCT,
+    as in Julia, not as numpy's zipped fancy indexing."""
+    from . import plan
+    if isinstance(d, SubDArray):
+        return d[subs]
+    sel, squeeze = plan.sel_normalize(tuple(subs), d.dims)
+    return SubDArray(d, sel, squeeze)
 
 
 # ---- convenience constructors (darray.jl:460-532) ----

@@ -1246,6 +1246,217 @@ def dgetindex(A, *ranges):
     return out
 
 
+# ------------------------------------- strided / index-vector selections
+def _copy_nd(dst, dst_shape, dst_sel, src, src_shape, src_sel, dtype):
+    """One da_copy_nd launch.  A side is (pointer, column-major buffer
+    shape, selection); selection None = the dense packed buffer of the
+    other side's selection shape."""
+    count = plan.sel_shape(dst_sel if dst_sel is not None else src_sel)
+    nd = len(count)
+    if any(c == 0 for c in count):
+        return
+    keep = []
+
+    def side(shape, sel):
+        if sel is None:
+            return (ctypes.c_uint64 * nd)(*count), None, None, None
+        start = (ctypes.c_int64 * nd)()
+        step = (ctypes.c_int64 * nd)()
+        idx = (ctypes.c_void_p * nd)()
+        for d, e in enumerate(sel):
+            if e[0] == "a":
+                start[d], step[d] = e[1], e[2]
+            else:
+                v = np.ascontiguousarray(e[1], dtype=np.int64)
+                keep.append(v)
+                idx[d] = v.ctypes.data
+        return (ctypes.c_uint64 * nd)(*shape), start, step, idx
+
+    dsh, dst0, dstp, didx = side(dst_shape, dst_sel)
+    ssh, sst0, sstp, sidx = side(src_shape, src_sel)
+    check(lib.da_copy_nd(dst, dsh, dst0, dstp, didx, src, ssh, sst0, sstp,
+                         sidx, (ctypes.c_uint64 * nd)(*count), nd,
+                         DTYPES[dtype]))
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= int(s)
+    return n
+
+
+def gather_sel(A, sels_all):
+    """Collective selection gather, the strided twin of gather_box: every
+    rank passes the SAME sels_all (sels_all[r] = the selection rank r
+    requests in A's global index space, see plan.sel_normalize, or None)
+    and receives A[sels_all[rank]] packed densely (column-major) in a
+    device buffer.  Returns (_Buf, shape) or (None, None).
+
+    Owners pack each outgoing piece with one da_copy_nd, the pieces move
+    in one grouped send/recv exchange, and the receiver places each with
+    one da_copy_nd at its positions; a local piece is a single da_copy_nd
+    from the chunk straight into the result."""
+    esz = DTYPE_SIZE[A.dtype]
+    me = A.rank
+    mysel = sels_all[me] if me < len(sels_all) else None
+    pieces = plan.sel_plan(A.idxs, A.ranks, sels_all)
+    out = oshape = None
+    if mysel is not None:
+        oshape = plan.sel_shape(mysel)
+        out = _Buf(max(_numel(oshape), 1) * esz)
+    sends, recvs = [], []
+    for src, dst, lsel, psel in pieces:
+        nbytes = _numel(plan.sel_shape(lsel)) * esz
+        if src == me and dst != me:
+            buf = _Buf(nbytes)
+            _copy_nd(buf.p, None, None, A._ptr(), A.lshape, lsel, A.dtype)
+            sends.append((buf, nbytes, dst))
+        elif dst == me and src != me:
+            recvs.append((_Buf(nbytes), nbytes, src, psel))
+    if sends or recvs:
+        check(lib.da_group_start())
+        for buf, nbytes, dst in sends:
+            check(lib.da_send(buf.p, nbytes, dst))
+        for buf, nbytes, src, _ in recvs:
+            check(lib.da_recv(buf.p, nbytes, src))
+        check(lib.da_group_end())
+    for src, dst, lsel, psel in pieces:
+        if src == me and dst == me:
+            _copy_nd(out.p, oshape, psel, A._ptr(), A.lshape, lsel, A.dtype)
+    for buf, _, _, psel in recvs:
+        _copy_nd(out.p, oshape, psel, buf.p, None, None, A.dtype)
+    check(lib.da_synchronize())
+    for buf, _, _ in sends:
+        buf.free()
+    for buf, _, _, _ in recvs:
+        buf.free()
+    return out, oshape
+
+
+def dgetindex_sel(A, sel):
+    """A[sel] for a strided / index-vector selection -> numpy array of
+    the selection's full (unsqueezed) shape on every rank; collective:
+    every rank requests the same selection, then does one D2H."""
+    buf, shape = gather_sel(A, [sel] * A.nranks)
+    out = np.empty(shape, dtype=np.dtype(NUMPY_DTYPES[A.dtype]), order="F")
+    if out.size:
+        check(lib.da_d2h(buf.p, out.ctypes.data_as(ctypes.c_void_p),
+                         out.size * DTYPE_SIZE[A.dtype]))
+    buf.free()
+    return out
+
+
+def _squeezed(shape, squeeze):
+    return tuple(n for d, n in enumerate(shape) if d not in squeeze)
+
+
+def dsub(A, sel, squeeze=()):
+    """DArray(view(A, sel)) (darray.jl:604-610): a new DArray holding the
+    selection, default-distributed; `squeeze` lists scalar-indexed
+    dimensions, dropped from the result.  Collective: each owner of a
+    result chunk requests that chunk's part of the selection."""
+    dims = _squeezed(plan.sel_shape(sel), squeeze)
+    if not dims:
+        raise DArrayError("a 0-dimensional selection has no DArray form")
+    R = DArray(dims, A.dtype)
+    sels = [None] * A.nranks
+    for c, r in enumerate(R.ranks):
+        box = plan.sel_expand(plan.sel_from_box(R.idxs[c]), len(sel),
+                              squeeze)
+        sels[r] = plan.compose(sel, box)
+    buf, _ = gather_sel(A, sels)
+    if buf is not None:
+        if R.lnumel:
+            check(lib.da_d2d(R._ptr(), buf.p,
+                             R.lnumel * DTYPE_SIZE[R.dtype]))
+            check(lib.da_synchronize())
+        buf.free()
+    return R
+
+
+def dsetindex_(D, sel, value, squeeze=()):
+    """D[sel] = value (copyto!(dest::SubOrDArray, src), darray.jl:679-687);
+    collective.  value is a scalar, a numpy array, a DArray or a
+    SubDArray of the selection's shape (full, or with the `squeeze`
+    dimensions dropped).  Every selected destination element must be
+    named once: a repeated index raises DArrayError on every rank before
+    any device work (a parallel scatter has no last-write-wins order).
+    Source and destination cuts need not match."""
+    from .darray import SubDArray
+    if plan.sel_has_duplicates(sel):
+        raise DArrayError("setindex: repeated destination index")
+    nd = len(sel)
+    full = plan.sel_shape(sel)
+    mine = (plan.sel_intersect(sel, D.lidx)
+            if D.lchunk is not None else None)
+    npdt = np.dtype(NUMPY_DTYPES[D.dtype])
+    esz = DTYPE_SIZE[D.dtype]
+
+    if isinstance(value, (DArray, SubDArray)):
+        S, vsel, vsq = ((value, plan.sel_full(value.dims), ())
+                        if isinstance(value, DArray)
+                        else (value.parent, value.sel, value.squeeze))
+        if S.dtype != D.dtype:
+            raise DArrayError("setindex: dtype mismatch %s vs %s"
+                              % (S.dtype, D.dtype))
+        if (_squeezed(plan.sel_shape(vsel), vsq)
+                != _squeezed(full, squeeze)):
+            raise DArrayError(
+                "setindex: source shape %r does not match selection %r"
+                % (_squeezed(plan.sel_shape(vsel), vsq),
+                   _squeezed(full, squeeze)))
+        sels = [None] * D.nranks
+        for c, r in enumerate(D.ranks):
+            hit = plan.sel_intersect(sel, D.idxs[c])
+            if hit is not None:
+                pos = tuple(e for d, e in enumerate(hit[1])
+                            if d not in squeeze)
+                sels[r] = plan.compose(
+                    vsel, plan.sel_expand(pos, len(vsel), vsq))
+        buf, _ = gather_sel(S, sels)
+        if buf is not None:
+            _copy_nd(D._ptr(), D.lshape, mine[0], buf.p, None, None,
+                     D.dtype)
+            check(lib.da_synchronize())
+            buf.free()
+        return D
+
+    if isinstance(value, np.ndarray) and value.ndim > 0:
+        if tuple(value.shape) == _squeezed(full, squeeze):
+            value = value.reshape(full, order="F")
+        if tuple(value.shape) != full:
+            raise DArrayError(
+                "setindex: value shape %r does not match selection %r"
+                % (tuple(value.shape), _squeezed(full, squeeze)))
+        if mine is None:
+            return D
+        sub = np.asfortranarray(
+            value[np.ix_(*[plan.sel_indices(e) for e in mine[1]])],
+            dtype=npdt)
+        buf = _Buf(sub.size * esz)
+        check(lib.da_h2d(buf.p, sub.ctypes.data_as(ctypes.c_void_p),
+                         sub.size * esz))
+        _copy_nd(D._ptr(), D.lshape, mine[0], buf.p, None, None, D.dtype)
+        check(lib.da_synchronize())
+        buf.free()
+        return D
+
+    # scalar: broadcast one device element (all-zero source steps); the
+    # value travels as its own bytes, so any i64 is exact
+    one = np.array([value]).astype(npdt)
+    if mine is None:
+        return D
+    buf = _Buf(esz)
+    check(lib.da_h2d(buf.p, one.ctypes.data_as(ctypes.c_void_p), esz))
+    cnt = plan.sel_shape(mine[0])
+    _copy_nd(D._ptr(), D.lshape, mine[0], buf.p, (1,) * nd,
+             tuple(("a", 0, 0, n) for n in cnt), D.dtype)
+    check(lib.da_synchronize())
+    buf.free()
+    return D
+
+
 def map_general(op, dest, src):
     """map!(f, dest, src) for MISMATCHED cuts (mapreduce.jl:5-12 with
     makelocal): gather src's piece of dest's index box, then map."""

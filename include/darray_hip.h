@@ -99,6 +99,50 @@ int da_d2d(void* dst, const void* src, uint64_t nbytes);
 int da_copy2d(void* dst, uint64_t dpitch, const void* src, uint64_t spitch,
               uint64_t width, uint64_t height);
 
+/* N-D selection-to-selection device copy: strided and index-vector
+ * getindex / setindex! / view materialisation (the SubArray paths of
+ * src/darray.jl:584-610, :661, :679-687).  Copies count[0] x .. x count[nd-1]
+ * elements between two column-major device buffers, each side with its own
+ * per-dimension selection (0-based):
+ *   dst[di_0(j_0) + dst_shape[0]*(di_1(j_1) + dst_shape[1]*( .. ))] =
+ *   src[si_0(j_0) + src_shape[0]*(si_1(j_1) + src_shape[1]*( .. ))]
+ * for 0 <= j_d < count[d], where an index is affine, start[d] + j*step[d]
+ * (step may be negative), or, when idx && idx[d], the explicit vector
+ * idx[d][j] of count[d] entries.  A NULL start / step / idx array means
+ * all 0 / all 1 / all affine, so a dense packed buffer is
+ * (shape = count, NULL, NULL, NULL).  One call therefore packs (gather),
+ * unpacks (scatter) or moves selection to selection.
+ *  - idx vectors are HOST pointers: validated on the host, staged to the
+ *    device on the rank's stream; the caller may free them on return.
+ *  - source step 0 with count > 1 broadcasts one element (scalar
+ *    assignment, singleton expansion).
+ *  - destination indices must be distinct per dimension (no step 0 with
+ *    count > 1, no repeated vector entry): a parallel scatter has no
+ *    last-write-wins order.
+ *  - any count[d] == 0 is a successful no-op; dst and src must not overlap.
+ * Raw 4- / 8-byte words are moved (bit-exact); offsets are 64-bit.
+ * da_copy_nd_plan is the host-only validator (no GPU work, callable
+ * before da_init): < 0 with a da_errstr message for nd outside
+ * 1..DA_COPY_MAXND, a bad dtype, any index outside [0, shape[d]) or a
+ * duplicate destination index; otherwise the kernel family the launch
+ * picks.  da_copy_nd runs it first, so with truthful shapes no argument
+ * combination touches memory outside the two buffers. */
+#define DA_COPY_MAXND 6
+/* runs: dimension 0 affine with step +1 on both sides (contiguous,
+ * coalesced stretches); general: everything else */
+enum da_copy_family { DA_COPY_RUNS = 0, DA_COPY_GENERAL = 1 };
+int da_copy_nd_plan(const uint64_t* dst_shape, const int64_t* dst_start,
+                    const int64_t* dst_step, const int64_t* const* dst_idx,
+                    const uint64_t* src_shape, const int64_t* src_start,
+                    const int64_t* src_step, const int64_t* const* src_idx,
+                    const uint64_t* count, int nd, int dtype);
+int da_copy_nd(void* dst, const uint64_t* dst_shape, const int64_t* dst_start,
+               const int64_t* dst_step, const int64_t* const* dst_idx,
+               const void* src, const uint64_t* src_shape,
+               const int64_t* src_start, const int64_t* src_step,
+               const int64_t* const* src_idx,
+               const uint64_t* count, int nd, int dtype);
+
 /* ---- constructors on device ------------------------------------------ */
 int da_fill(void* chunk, double v, uint64_t n, int dtype);   /* dzeros/dones/dfill/fill!, darray.jl:468-494,822-827 */
 /* Philox4x32-10 fill; element mapping documented in oracle/philox.py.
