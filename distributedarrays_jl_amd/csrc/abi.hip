@@ -85,6 +85,11 @@ int da_init(int device, int rank, int nranks, const char* rccl_uid_path) {
                                          hipEventDisableTiming));
     DA_CHECK_HIP(hipMalloc(&st().red_ticket, sizeof(unsigned int)));
     DA_CHECK_HIP(hipMemset(st().red_ticket, 0, sizeof(unsigned int)));
+    st().red_base = 0;
+    DA_CHECK_HIP(hipHostMalloc(&st().red_host, 16, hipHostMallocDefault));
+    memset(st().red_host, 0, 16);
+    DA_CHECK_HIP(hipHostGetDevicePointer(&st().red_host_dev,
+                                         st().red_host, 0));
     st().device = device;
     st().rank = rank;
     st().nranks = nranks;
@@ -138,6 +143,8 @@ int da_shutdown(void) {
     }
     if (st().red_ticket) { (void)hipFree(st().red_ticket);
                            st().red_ticket = nullptr; }
+    if (st().red_host) { (void)hipHostFree(st().red_host);
+                         st().red_host = st().red_host_dev = nullptr; }
     if (st().ev_main) { (void)hipEventDestroy(st().ev_main); st().ev_main = nullptr; }
     if (st().ev_comm) { (void)hipEventDestroy(st().ev_comm); st().ev_comm = nullptr; }
     if (st().comm_stream) { (void)hipStreamDestroy(st().comm_stream);

@@ -34,9 +34,16 @@ struct State {
     // reduction partials buffer
     void* partials = nullptr;
     size_t partials_bytes = 0;
-    // fused-reduce fan-in ticket (dedicated 4 bytes, zeroed at init;
-    // must NOT live in `partials`, which dims-reduce reuses as slabs)
+    // single-launch reduce fan-in ticket (dedicated 4 bytes, zeroed at
+    // init and never reset; must NOT live in `partials`, which
+    // dims-reduce reuses as slabs).  red_base is the value the counter
+    // holds before the next launch (kernels_reduce.hip, ticket invariant)
     unsigned int* red_ticket = nullptr;
+    unsigned int red_base = 0;
+    // pinned host slot (8 bytes) the flat reduce / count kernels write
+    // their result to, and the device's address of it
+    void* red_host = nullptr;
+    void* red_host_dev = nullptr;
     std::mutex mem_mtx;
     std::unordered_map<void*, uint64_t> allocs;
     uint64_t bytes_in_use = 0;

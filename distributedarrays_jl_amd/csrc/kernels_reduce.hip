@@ -4,8 +4,10 @@
 // /root/reference/src/mapreduce.jl:29-35 (and the specials :97-131).
 // Two-stage tree: grid-stride vectorized loads -> per-thread partial ->
 // 64-wide wavefront __shfl_down reduction -> LDS across the block's 4
-// waves -> one partial per block; a single-block second kernel folds the
-// block partials.  Integer add/mul wrap mod 2^64, so any order is
+// waves -> one partial per block; the last block to finish folds the
+// block partials in the same launch (DA_RED_FUSED=0: a single-block
+// second kernel does, in the same order) and writes the result to a
+// pinned host slot.  Integer add/mul wrap mod 2^64, so any order is
 // bit-exact (test/darray.jl:286-294 exactness contract); float order is
 // a tree, within the 1e-6 contract of BASELINE.json (the reference's own
 // fold order is likewise unspecified: docs/src/index.md:208-236).
@@ -106,9 +108,9 @@ __device__ __forceinline__ int64_t mapf(int mapop, int64_t x) {
     return x;
 }
 
+// `lds`: RTPB/64 workgroup-shared elements, one per wave.
 template <typename T>
-__device__ __forceinline__ T block_reduce(int redop, T v) {
-    __shared__ T lds[RTPB / 64];
+__device__ __forceinline__ T block_reduce_in(int redop, T v, T* lds) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
         v = red_comb(redop, v, (T)__shfl_down(v, off, 64));
@@ -126,6 +128,34 @@ __device__ __forceinline__ T block_reduce(int redop, T v) {
     return v;
 }
 
+template <typename T>
+__device__ __forceinline__ T block_reduce(int redop, T v) {
+    __shared__ T lds[RTPB / 64];
+    return block_reduce_in(redop, v, lds);
+}
+
+// The grid-stride accumulate loop of every flat reduce kernel: W-wide
+// vector loads over the first n/W*W elements, then the scalar tail.
+// fold(acc, x) absorbs one source element.  Every caller is launched
+// with RTPB threads per block; the constant keeps the stride in SGPRs.
+template <int W, typename T, typename A, typename F>
+__device__ __forceinline__ A grid_accumulate(const T* __restrict__ src,
+                                             uint64_t n, A acc, F fold) {
+    uint64_t i = (uint64_t)blockIdx.x * RTPB + threadIdx.x;
+    uint64_t stride = (uint64_t)gridDim.x * RTPB;
+    using V = T __attribute__((ext_vector_type(W)));
+    uint64_t nv = n / W;
+    const V* sv = reinterpret_cast<const V*>(src);
+    for (uint64_t j = i; j < nv; j += stride) {
+        V v = sv[j];
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc = fold(acc, (T)v[k]);
+    }
+    for (uint64_t j = W * nv + i; j < n; j += stride)
+        acc = fold(acc, src[j]);
+    return acc;
+}
+
 // MOP/ROP >= 0 fold the op switches at compile time for the hot
 // combos (same trick as map_fixed/dims-reduce); -1 = runtime args.
 template <typename T, int MOP = -1, int ROP = -1>
@@ -133,19 +163,8 @@ __global__ void reduce_stage1(int mapop, int redop, const T* __restrict__ src,
                               uint64_t n, T* __restrict__ partials) {
     if (MOP >= 0) mapop = MOP;
     if (ROP >= 0) redop = ROP;
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    T acc = RedIdent<T>::get(redop);
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* sv = reinterpret_cast<const V*>(src);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.x));
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.y));
-    }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride)
-        acc = red_comb(redop, acc, mapf<T>(mapop, src[j]));
+    T acc = grid_accumulate<2>(src, n, RedIdent<T>::get(redop),
+        [=](T a, T x) { return red_comb(redop, a, mapf<T>(mapop, x)); });
     acc = block_reduce(redop, acc);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
@@ -158,80 +177,87 @@ __global__ void reduce_stage1_v4(int mapop, int redop,
                                  T* __restrict__ partials) {
     if (MOP >= 0) mapop = MOP;
     if (ROP >= 0) redop = ROP;
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    T acc = RedIdent<T>::get(redop);
-    using V = T __attribute__((ext_vector_type(4)));
-    uint64_t nv = n / 4;
-    const V* sv = reinterpret_cast<const V*>(src);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.x));
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.y));
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.z));
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.w));
-    }
-    for (uint64_t j = 4 * nv + i; j < n; j += stride)
-        acc = red_comb(redop, acc, mapf<T>(mapop, src[j]));
+    T acc = grid_accumulate<4>(src, n, RedIdent<T>::get(redop),
+        [=](T a, T x) { return red_comb(redop, a, mapf<T>(mapop, x)); });
     acc = block_reduce(redop, acc);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
-// Fused single-kernel reduce: stage-1 blocks publish their partial with
-// an agent-scope release and take a ticket; the LAST arriver acquires,
-// folds all partials and writes the result — the fan-in form of the
-// guide's split-K seam recipe (cdna_hip_programming.md §5, "In-launch
-// split-K reduction"; no grid-wide wait, so residency is irrelevant).
-// The ticket counter lives in the partials buffer, is zeroed at
-// allocation, and is reset by the last arriver; same-stream ordering
-// makes the reset visible to the next launch.
-template <typename T>
-__global__ void reduce_fused(int mapop, int redop, const T* __restrict__ src,
-                             uint64_t n, T* __restrict__ partials,
-                             unsigned int* __restrict__ ticket,
-                             T* __restrict__ out) {
-    __shared__ int is_last;
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    T acc = RedIdent<T>::get(redop);
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* sv = reinterpret_cast<const V*>(src);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.x));
-        acc = red_comb(redop, acc, mapf<T>(mapop, (T)v.y));
-    }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride)
-        acc = red_comb(redop, acc, mapf<T>(mapop, src[j]));
-    acc = block_reduce(redop, acc);
-    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-    // publish: wait the partial store, release, ticket (guide order:
-    // fence THEN fetch_add, with the asm vmcnt wait restated after the
-    // fence — ROCm 7.2 drops the post-wbl2 wait otherwise)
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+// ---- single-launch fan-in (cdna_hip_programming.md §5, "In-launch
+// split-K reduction", in its fence-free form; §6 Guideline 16 R1).
+// Each block's payload is ONE partial of <= 8 bytes, so it is published
+// by a relaxed agent-scope atomic store — a write-through (sc1) store
+// that needs no release fence — drained by the storing wave's
+// s_waitcnt vmcnt(0) before that same lane takes its ticket.  Only the
+// last arriver pays a fence: one agent-scope acquire, then plain loads
+// of all partials in reduce_stage2's fold order (thread t folds
+// t, t+256, ...; then block_reduce), so both paths give the same bits.
+// No block waits for another, so residency is irrelevant.
+//
+// Ticket invariant: the counter is zeroed once in da_init and never
+// reset.  Every launch of g blocks adds exactly g, and launches of the
+// one library stream run in order, so before a launch the counter
+// equals State::red_base (mod 2^32), which the host advances by g per
+// launch.  A block is last iff ticket - base == g - 1 in unsigned
+// arithmetic; that holds across wrap-around, any sequence of grid
+// sizes, and interleaved dtypes / reduce / count calls.
+template <typename A>
+__device__ __forceinline__ void publish_partial(A* p, A v) {
+    if constexpr (sizeof(A) == 8)
+        __hip_atomic_store((unsigned long long*)p,
+                           __builtin_bit_cast(unsigned long long, v),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+        __hip_atomic_store((unsigned int*)p,
+                           __builtin_bit_cast(unsigned int, v),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// `acc`: the block's partial (valid in thread 0).  `sh`: RTPB/64 + 1
+// shared elements — block_reduce_in's scratch plus the "I am last"
+// flag, kept in ONE __shared__ object.  Reusing sh[0..3] for the final
+// fold is safe: wave 0 read them before it wrote the flag, and every
+// other wave writes them again only after the barriers below.
+template <typename A>
+__device__ __forceinline__ void fanin_finish(int redop, A acc, A* partials,
+                                             unsigned int* ticket,
+                                             unsigned int base, A* out,
+                                             A* sh) {
     if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        publish_partial(partials + blockIdx.x, acc);
         __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned int t = __hip_atomic_fetch_add(
             ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (t == gridDim.x - 1);
+        sh[RTPB / 64] = (t - base == gridDim.x - 1) ? (A)1 : (A)0;
     }
     __syncthreads();
-    if (!is_last) return;
-    if (threadIdx.x == 0)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    __syncthreads();
-    T facc = RedIdent<T>::get(redop);
-    for (unsigned int j = threadIdx.x; j < gridDim.x; j += blockDim.x)
-        facc = red_comb(redop, facc, partials[j]);
-    __syncthreads();   // block_reduce LDS reused after the first pass
-    facc = block_reduce(redop, facc);
+    if (sh[RTPB / 64] == (A)0) return;
+    // guide order: the fence, that lane's vmcnt wait, the barrier
     if (threadIdx.x == 0) {
-        out[0] = facc;
-        *ticket = 0;   // next launch on this stream sees 0
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
+    __syncthreads();
+    A facc = RedIdent<A>::get(redop);
+    for (unsigned int j = threadIdx.x; j < gridDim.x; j += RTPB)
+        facc = red_comb(redop, facc, partials[j]);
+    facc = block_reduce_in(redop, facc, sh);
+    if (threadIdx.x == 0) out[0] = facc;
+}
+
+// `partials` is deliberately not __restrict__/const: its loads must stay
+// vector loads behind the acquire.  `out` is host-visible pinned memory.
+template <typename T, int MOP = -1, int ROP = -1>
+__global__ void reduce_fused(int mapop, int redop, const T* __restrict__ src,
+                             uint64_t n, T* partials, unsigned int* ticket,
+                             unsigned int base, T* out) {
+    if (MOP >= 0) mapop = MOP;
+    if (ROP >= 0) redop = ROP;
+    __shared__ T sh[RTPB / 64 + 1];
+    T acc = grid_accumulate<2>(src, n, RedIdent<T>::get(redop),
+        [=](T a, T x) { return red_comb(redop, a, mapf<T>(mapop, x)); });
+    acc = block_reduce_in(redop, acc, sh);
+    fanin_finish(redop, acc, partials, ticket, base, out, sh);
 }
 
 template <typename T>
@@ -244,6 +270,37 @@ __global__ void reduce_stage2(int redop, const T* __restrict__ partials,
     if (threadIdx.x == 0) out[0] = acc;
 }
 
+// DA_RED_FUSED: unset or nonzero = single launch; 0 = stage 1 + stage 2.
+static inline bool reduce_fused_on() {
+    static int v = -1;
+    if (v < 0) {
+        const char* e = getenv("DA_RED_FUSED");
+        v = e ? (atoi(e) != 0) : 1;
+    }
+    return v == 1;
+}
+
+template <typename T> struct FlatArgs {
+    bool fused;
+    int grid, mapop, redop;
+    const T* src;
+    uint64_t n;
+    T *parts, *out;
+    hipStream_t s;
+};
+
+template <typename T, int MOP, int ROP>
+static void launch_flat(const FlatArgs<T>& a) {
+    if (a.fused)
+        hipLaunchKernelGGL((reduce_fused<T, MOP, ROP>), dim3(a.grid),
+                           dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src, a.n,
+                           a.parts, st().red_ticket, st().red_base, a.out);
+    else
+        hipLaunchKernelGGL((reduce_stage1<T, MOP, ROP>), dim3(a.grid),
+                           dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src, a.n,
+                           a.parts);
+}
+
 template <typename T>
 static int do_reduce(int mapop, int redop, const T* src, uint64_t n,
                      void* out_host, hipStream_t s) {
@@ -254,55 +311,37 @@ static int do_reduce(int mapop, int redop, const T* src, uint64_t n,
     bool v4 = reduce_v4();
     uint64_t want = (n / (v4 ? 4 : 2) + RTPB - 1) / RTPB;
     int g = reduce_grid(want);
-    int rc = ensure_partials((RMAXB + 1) * sizeof(double));
+    int rc = ensure_partials(RMAXB * sizeof(double));
     if (rc) return rc;
-    T* parts = (T*)st().partials;
-    T* dout = (T*)((double*)st().partials + RMAXB);
-    unsigned int* ticket = st().red_ticket;
-    static int fused = -1;
-    if (fused < 0) {
-        const char* e = getenv("DA_RED_FUSED");
-        fused = e ? atoi(e) : 0;   // measured SLOWER at 2048 blocks (profiles)
-    }
-    if (fused && !v4) {
-        hipLaunchKernelGGL(reduce_fused<T>, dim3(g), dim3(RTPB), 0, s,
-                           mapop, redop, src, n, parts, ticket, dout);
-        DA_CHECK_HIP(hipGetLastError());
+    // the result lands in the pinned host slot: no device-to-host copy
+    // command follows the kernels
+    FlatArgs<T> a = {reduce_fused_on() && !v4, g, mapop, redop, src, n,
+                     (T*)st().partials, (T*)st().red_host_dev, s};
+    if (v4)
+        hipLaunchKernelGGL((reduce_stage1_v4<T>), dim3(g), dim3(RTPB),
+                           0, s, mapop, redop, src, n, a.parts);
+    else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_ADD)
+        launch_flat<T, DA_REDF_IDENTITY, DA_RED_ADD>(a);
+    else if (mapop == DA_REDF_ABS2 && redop == DA_RED_ADD)
+        launch_flat<T, DA_REDF_ABS2, DA_RED_ADD>(a);
+    else if (mapop == DA_REDF_ABS && redop == DA_RED_ADD)
+        launch_flat<T, DA_REDF_ABS, DA_RED_ADD>(a);
+    else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_MAX)
+        launch_flat<T, DA_REDF_IDENTITY, DA_RED_MAX>(a);
+    else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_MIN)
+        launch_flat<T, DA_REDF_IDENTITY, DA_RED_MIN>(a);
+    else
+        launch_flat<T, -1, -1>(a);
+    DA_CHECK_HIP(hipGetLastError());
+    if (a.fused) {
+        st().red_base += (unsigned int)g;
     } else {
-        if (v4)
-            hipLaunchKernelGGL((reduce_stage1_v4<T>), dim3(g), dim3(RTPB),
-                               0, s, mapop, redop, src, n, parts);
-        else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_ADD)
-            hipLaunchKernelGGL((reduce_stage1<T, DA_REDF_IDENTITY,
-                                DA_RED_ADD>), dim3(g), dim3(RTPB), 0, s,
-                               mapop, redop, src, n, parts);
-        else if (mapop == DA_REDF_ABS2 && redop == DA_RED_ADD)
-            hipLaunchKernelGGL((reduce_stage1<T, DA_REDF_ABS2,
-                                DA_RED_ADD>), dim3(g), dim3(RTPB), 0, s,
-                               mapop, redop, src, n, parts);
-        else if (mapop == DA_REDF_ABS && redop == DA_RED_ADD)
-            hipLaunchKernelGGL((reduce_stage1<T, DA_REDF_ABS,
-                                DA_RED_ADD>), dim3(g), dim3(RTPB), 0, s,
-                               mapop, redop, src, n, parts);
-        else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_MAX)
-            hipLaunchKernelGGL((reduce_stage1<T, DA_REDF_IDENTITY,
-                                DA_RED_MAX>), dim3(g), dim3(RTPB), 0, s,
-                               mapop, redop, src, n, parts);
-        else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_MIN)
-            hipLaunchKernelGGL((reduce_stage1<T, DA_REDF_IDENTITY,
-                                DA_RED_MIN>), dim3(g), dim3(RTPB), 0, s,
-                               mapop, redop, src, n, parts);
-        else
-            hipLaunchKernelGGL((reduce_stage1<T>), dim3(g), dim3(RTPB),
-                               0, s, mapop, redop, src, n, parts);
-        DA_CHECK_HIP(hipGetLastError());
         hipLaunchKernelGGL(reduce_stage2<T>, dim3(1), dim3(RTPB), 0, s,
-                           redop, parts, g, dout);
+                           redop, a.parts, g, a.out);
         DA_CHECK_HIP(hipGetLastError());
     }
-    DA_CHECK_HIP(hipMemcpyAsync(out_host, dout, sizeof(T),
-                                hipMemcpyDeviceToHost, s));
     DA_CHECK_HIP(hipStreamSynchronize(s));
+    memcpy(out_host, st().red_host, sizeof(T));
     return 0;
 }
 
@@ -325,39 +364,49 @@ __device__ __forceinline__ int64_t predf<int64_t>(int mapop, int64_t x) {
 template <typename T>
 __global__ void count_stage1(int mapop, const T* __restrict__ src,
                              uint64_t n, int64_t* __restrict__ partials) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    int64_t acc = 0;
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* sv = reinterpret_cast<const V*>(src);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        acc += predf<T>(mapop, (T)v.x) + predf<T>(mapop, (T)v.y);
-    }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride)
-        acc += predf<T>(mapop, src[j]);
+    int64_t acc = grid_accumulate<2>(src, n, (int64_t)0,
+        [=](int64_t a, T x) { return a + predf<T>(mapop, x); });
     acc = block_reduce(DA_RED_ADD, acc);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+// single-launch count: count_stage1's loop, then the fan-in of
+// reduce_fused on the int64 partials
+template <typename T>
+__global__ void count_fused(int mapop, const T* __restrict__ src, uint64_t n,
+                            int64_t* partials, unsigned int* ticket,
+                            unsigned int base, int64_t* out) {
+    __shared__ int64_t sh[RTPB / 64 + 1];
+    int64_t acc = grid_accumulate<2>(src, n, (int64_t)0,
+        [=](int64_t a, T x) { return a + predf<T>(mapop, x); });
+    acc = block_reduce_in((int)DA_RED_ADD, acc, sh);
+    fanin_finish((int)DA_RED_ADD, acc, partials, ticket, base, out, sh);
 }
 
 template <typename T>
 static int do_count(int mapop, const T* src, uint64_t n, int64_t* out_host,
                     hipStream_t s) {
     int g = reduce_grid((n / 2 + RTPB - 1) / RTPB);
-    int rc = ensure_partials((RMAXB + 1) * sizeof(double));
+    int rc = ensure_partials(RMAXB * sizeof(double));
     if (rc) return rc;
     int64_t* parts = (int64_t*)st().partials;
-    int64_t* dout = parts + RMAXB;
-    hipLaunchKernelGGL(count_stage1<T>, dim3(g), dim3(RTPB), 0, s,
-                       mapop, src, n, parts);
-    DA_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(reduce_stage2<int64_t>, dim3(1), dim3(RTPB), 0, s,
-                       (int)DA_RED_ADD, parts, g, dout);
-    DA_CHECK_HIP(hipGetLastError());
-    DA_CHECK_HIP(hipMemcpyAsync(out_host, dout, sizeof(int64_t),
-                                hipMemcpyDeviceToHost, s));
+    int64_t* out = (int64_t*)st().red_host_dev;
+    if (reduce_fused_on()) {
+        hipLaunchKernelGGL(count_fused<T>, dim3(g), dim3(RTPB), 0, s,
+                           mapop, src, n, parts, st().red_ticket,
+                           st().red_base, out);
+        DA_CHECK_HIP(hipGetLastError());
+        st().red_base += (unsigned int)g;
+    } else {
+        hipLaunchKernelGGL(count_stage1<T>, dim3(g), dim3(RTPB), 0, s,
+                           mapop, src, n, parts);
+        DA_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(reduce_stage2<int64_t>, dim3(1), dim3(RTPB), 0, s,
+                           (int)DA_RED_ADD, parts, g, out);
+        DA_CHECK_HIP(hipGetLastError());
+    }
     DA_CHECK_HIP(hipStreamSynchronize(s));
+    memcpy(out_host, st().red_host, sizeof(int64_t));
     return 0;
 }
 
