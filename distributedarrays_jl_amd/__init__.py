@@ -23,7 +23,7 @@ from .darray import (DArray, dzeros, dones, dfill, drand, drandn,
                      dfromfunction, SubDArray, dview)
 from .ops import (map_, dmap, map2_, elementwise, map2_scalar_, elementwise_scalar, broadcast_fma, axpy_,
                   add_, scale_, mapreduce, dsum, dprod, dmaximum, dminimum,
-                  dextrema, dmean, dcount, dall, dany, ddot, dnorm, dmatmul, dreduce_dims,
+                  dextrema, dmean, dvar, dstd, dcount, dall, dany, ddot, dnorm, dmatmul, dreduce_dims,
                   dsum_dims, dprod_dims, dmaximum_dims, dminimum_dims,
                   dmean_dims, dmatvec, dmatvec_adj, gather_box, map_general,
                   map_localparts, map_localparts_, redistribute,
@@ -40,7 +40,7 @@ __all__ = [
     "ddata", "dgather", "locate", "allowscalar", "dfromfunction",
     "map_", "dmap", "map2_", "elementwise", "map2_scalar_", "elementwise_scalar", "broadcast_fma", "axpy_",
     "add_", "scale_", "mapreduce", "dsum", "dprod", "dmaximum",
-    "dminimum", "dextrema", "dmean", "dcount", "dall", "dany", "ddot", "dnorm", "dmatmul",
+    "dminimum", "dextrema", "dmean", "dvar", "dstd", "dcount", "dall", "dany", "ddot", "dnorm", "dmatmul",
     "dreduce_dims", "dsum_dims", "dprod_dims", "dmaximum_dims",
     "dminimum_dims", "dmean_dims", "dmatvec", "dmatvec_adj",
     "map_localparts", "map_localparts_", "redistribute",

@@ -344,6 +344,30 @@ int da_expr(const int32_t* prog, int prog_len, void* dst,
                        st().stream);
 }
 
+int da_expr_reduce(const int32_t* prog, int prog_len,
+                   const uint64_t* dims, int nd,
+                   void* const* srcs, const uint64_t* src_strides, int nsrcs,
+                   const double* consts, int nconsts, uint64_t n, int dtype,
+                   int redop, void* out) {
+    DA_REQUIRE_INIT();
+    if (redop < 0)
+        return set_err(-3, "da_expr_reduce: bad redop %d", redop);
+    return launch_expr_reduce(prog, prog_len, dims, nd, srcs, src_strides,
+                              nsrcs, consts, nconsts, n, dtype, redop, out,
+                              st().stream);
+}
+
+int da_expr_count(const int32_t* prog, int prog_len,
+                  const uint64_t* dims, int nd,
+                  void* const* srcs, const uint64_t* src_strides, int nsrcs,
+                  const double* consts, int nconsts, uint64_t n, int dtype,
+                  int64_t* out) {
+    DA_REQUIRE_INIT();
+    return launch_expr_reduce(prog, prog_len, dims, nd, srcs, src_strides,
+                              nsrcs, consts, nconsts, n, dtype,
+                              DA_EXPR_COUNT, out, st().stream);
+}
+
 /* 1 = JIT ready (unused yet), 2 = active, -1 = failed (interpreter);
  * DA_EXPR_JIT=0 disables per call.  da_expr_jit_errstr() holds the
  * last hipRTC diagnostic. */

@@ -91,6 +91,25 @@ inline size_t dtype_size(int dtype) {
 int ensure_scratch(size_t bytes);
 int ensure_partials(size_t bytes);
 
+// ---- flat-reduce plumbing shared by da_reduce, da_count and the fused
+// expression reduce (kernels_reduce.hip)
+constexpr int RMAXB = 8192;        // block partials (fits scratch)
+int reduce_grid(uint64_t want);    // min(want, DA_RBLOCKS cap), >= 1
+bool reduce_fused_on();            // DA_RED_FUSED != 0
+int reduce_stage2_launch(int redop, int g, int dtype, hipStream_t s);
+int reduce_result(void* out_host, size_t bytes, hipStream_t s);
+
+// Ticket hand-out of EVERY single-launch fan-in kernel (ticket invariant,
+// reduce_core.hpp): launch(base) starts a g-block kernel whose blocks
+// each take one ticket against `base` and returns its hipError_t; only a
+// launch that succeeded advances red_base.
+template <typename L>
+inline int fanin_launch(int g, L launch) {
+    DA_CHECK_HIP(launch(st().red_base));
+    st().red_base += (unsigned int)g;
+    return 0;
+}
+
 // kernel-side entry points (implemented in kernels_*.hip)
 int launch_fill(void* chunk, double v, uint64_t n, int dtype, hipStream_t s);
 int launch_rand(void* chunk, uint64_t n, int dtype, uint64_t seed, int kind,
@@ -115,6 +134,24 @@ int launch_expr_jit(const int32_t* prog, int plen, void* dst,
                     void* const* srcs, const uint64_t* src_strides,
                     int nsrcs, const double* consts, int nconsts,
                     uint64_t n, int dtype, hipStream_t s);
+// Fused mapreduce over a program (kernels_expr.hip): redop is a da_redop,
+// or DA_EXPR_COUNT for the exact count of nonzero terms (out: int64_t).
+constexpr int DA_EXPR_COUNT = -1;
+int validate_expr(const char* who, const int32_t* prog, int plen, int nsrcs,
+                  int nconsts);
+int launch_expr_reduce(const int32_t* prog, int plen, const uint64_t* dims,
+                       int nd, void* const* srcs,
+                       const uint64_t* src_strides, int nsrcs,
+                       const double* consts, int nconsts, uint64_t n,
+                       int dtype, int redop, void* out_host, hipStream_t s);
+// hipRTC path of the above: launches only the g-block first kernel (with
+// the in-kernel fan-in when `fused`); 0 / 1 / <0 as launch_expr_jit
+int launch_expr_reduce_jit(const int32_t* prog, int plen,
+                           const uint64_t* dims, int nd, void* const* srcs,
+                           const uint64_t* src_strides, int nsrcs,
+                           const double* consts, int nconsts, uint64_t n,
+                           int dtype, int redop, int g, bool fused,
+                           hipStream_t s);
 int expr_jit_state();
 const char* expr_jit_err();
 int launch_transpose(void* dst, const void* src, uint64_t m, uint64_t n,

@@ -246,23 +246,106 @@ std::string gen_source(const int32_t* prog, int plen, int dtype, int nd,
     return s;
 }
 
-int jit_get(const std::string& src, hipFunction_t* out) {
-    std::lock_guard<std::mutex> g(g_jit_mtx);
-    auto it = g_jit_cache.find(src);
-    if (it != g_jit_cache.end()) {
-        *out = it->second.fn;
-        return 0;
+const char* JRARGS_DECL =
+    "struct JRArgs {\n"
+    "  JArgs a;\n"
+    "  void* partials;\n"
+    "  unsigned int* ticket;\n"
+    "  void* out;\n"
+    "  unsigned int base;\n"
+    "  int fused;\n"
+    "};\n";
+
+// Fused mapreduce kernel for one program: evalx (gen_eval, unchanged)
+// feeds the accumulate loop, block tree and fan-in of reduce_core.hpp.
+// redop (or the count) is baked in, so the red_comb switch folds.  The
+// loop is da_reduce's — thread i absorbs terms 2j, 2j+1 for j = i,
+// i+stride, ..., then the scalar tail — for EVERY program and layout:
+// the fold order is the contract (bits of materialise-then-reduce), so
+// there is no prog_heavy unroll choice here.
+std::string gen_reduce_source(const int32_t* prog, int plen, int dtype,
+                              int nd, int nsrcs, bool strided, int redop) {
+    const bool count = redop == DA_EXPR_COUNT;
+    const char* tname = dtype == DA_F64 ? "double"
+                        : dtype == DA_F32 ? "float" : "long long";
+    // the accumulator: int64_t for i64 folds and every count
+    // (red_comb's wrapping overload), else the element type
+    const char* aname = (count || dtype == DA_I64) ? "int64_t" : tname;
+    const int rop = count ? (int)DA_RED_ADD : redop;
+    std::string s =
+        "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n"
+        "#include \"mapops.hpp\"\n#include \"reduce_core.hpp\"\n";
+    s += JARGS_DECL;
+    s += JRARGS_DECL;
+    s += gen_eval(prog, plen, tname, dtype == DA_I64, strided);
+    char buf[4096];
+    if (strided) {
+        // today's strided ejit decode, per element
+        int K = nsrcs > 0 ? nsrcs : 1;
+        snprintf(buf, sizeof(buf),
+            "static __device__ __forceinline__ %s term(const JArgs& a, "
+            "unsigned long long i) {\n"
+            "  unsigned int idx[%d]; unsigned int rem = (unsigned int)i;\n"
+            "  for (int d = 0; d < %d; ++d) { idx[d] = rem %% a.dims[d]; "
+            "rem /= a.dims[d]; }\n"
+            "  unsigned long long off[%d];\n"
+            "  for (int k = 0; k < %d; ++k) { off[k] = 0;\n"
+            "    for (int d = 0; d < %d; ++d) off[k] += "
+            "(unsigned long long)idx[d] * a.str[k][d]; }\n"
+            "  return evalx(a, off);\n"
+            "}\n", tname, nd, nd, K, K, nd);
+    } else {
+        snprintf(buf, sizeof(buf),
+            "static __device__ __forceinline__ %s term(const JArgs& a, "
+            "unsigned long long i) { return evalx(a, i); }\n", tname);
     }
-    if (g_jit_cache.size() >= 256) {
-        // bound module memory for workloads generating unbounded
-        // distinct programs; recompilation repopulates on demand.
-        // Drain the device first — a cached kernel may be in flight.
-        (void)hipDeviceSynchronize();
-        for (auto& kv : g_jit_cache) hipModuleUnload(kv.second.mod);
-        g_jit_cache.clear();
-    }
+    s += buf;
+    if (count)
+        snprintf(buf, sizeof(buf),
+            "#define ABSORB(acc, x) ((acc) + ((x) != (%s)0 ? 1 : 0))\n",
+            tname);
+    else
+        snprintf(buf, sizeof(buf),
+            "#define ABSORB(acc, x) da::red_comb(%d, (acc), (%s)(x))\n",
+            rop, aname);
+    s += buf;
+    snprintf(buf, sizeof(buf),
+        "/*%s*/extern \"C\" __global__ void ejit(JRArgs r) {\n"
+        "  const JArgs& a = r.a;\n"
+        "  __shared__ %s sh[da::RTPB / 64 + 1];\n"
+        "  unsigned long long i = (unsigned long long)blockIdx.x * "
+        "da::RTPB + threadIdx.x;\n"
+        "  unsigned long long st = (unsigned long long)gridDim.x * "
+        "da::RTPB;\n"
+        "  %s acc = da::RedIdent<%s>::get(%d);\n"
+        "  unsigned long long nv = a.n / 2;\n"
+        "  for (unsigned long long j = i; j < nv; j += st) {\n"
+        "    %s r0 = term(a, 2 * j);\n"
+        "    %s r1 = term(a, 2 * j + 1);\n"
+        "    acc = ABSORB(acc, r0);\n"
+        "    acc = ABSORB(acc, r1);\n"
+        "  }\n"
+        "  for (unsigned long long j = 2 * nv + i; j < a.n; j += st)\n"
+        "    acc = ABSORB(acc, term(a, j));\n"
+        "  acc = da::block_reduce_in(%d, acc, sh);\n"
+        "  if (r.fused)\n"
+        "    da::fanin_finish(%d, acc, (%s*)r.partials, r.ticket, r.base, "
+        "(%s*)r.out, sh);\n"
+        "  else if (threadIdx.x == 0)\n"
+        "    ((%s*)r.partials)[blockIdx.x] = acc;\n"
+        "}\n",
+        count ? "count" : "reduce", aname, aname, aname, rop, tname, tname,
+        rop, rop, aname, aname, aname);
+    s += buf;
+    return s;
+}
+
+// hipRTC-compile one generated source against the embedded device headers
+// (a pure compiler call: no GPU needed).  0 ok, -1 failure with the
+// diagnostic in g_jit_err; `code` (may be null) receives the code object.
+int jit_compile(const std::string& src, std::vector<char>* code) {
     const char* hdr_names[] = {"stdint.h", "darray_hip.h", "mapops.hpp",
-                               "fastmath.hpp"};
+                               "fastmath.hpp", "reduce_core.hpp"};
     const char* stdint_stub =
         "#pragma once\n"
         "typedef __INT8_TYPE__ int8_t;\ntypedef __UINT8_TYPE__ uint8_t;\n"
@@ -270,10 +353,11 @@ int jit_get(const std::string& src, hipFunction_t* out) {
         "typedef __INT32_TYPE__ int32_t;\ntypedef __UINT32_TYPE__ uint32_t;\n"
         "typedef __INT64_TYPE__ int64_t;\ntypedef __UINT64_TYPE__ uint64_t;\n";
     const char* hdrs[] = {stdint_stub, embedded_darray_hip_h,
-                          embedded_mapops_hpp, embedded_fastmath_hpp};
+                          embedded_mapops_hpp, embedded_fastmath_hpp,
+                          embedded_reduce_core_hpp};
     hiprtcProgram prog;
     hiprtcResult rc = hiprtcCreateProgram(&prog, src.c_str(), "ejit.cu",
-                                          4, hdrs, hdr_names);
+                                          5, hdrs, hdr_names);
     if (rc != HIPRTC_SUCCESS) {
         snprintf(g_jit_err, sizeof(g_jit_err), "hiprtcCreateProgram: %s",
                  hiprtcGetErrorString(rc));
@@ -292,11 +376,33 @@ int jit_get(const std::string& src, hipFunction_t* out) {
         hiprtcDestroyProgram(&prog);
         return -1;
     }
-    size_t csz = 0;
-    hiprtcGetCodeSize(prog, &csz);
-    std::vector<char> code(csz);
-    hiprtcGetCode(prog, code.data());
+    if (code) {
+        size_t csz = 0;
+        hiprtcGetCodeSize(prog, &csz);
+        code->resize(csz);
+        hiprtcGetCode(prog, code->data());
+    }
     hiprtcDestroyProgram(&prog);
+    return 0;
+}
+
+int jit_get(const std::string& src, hipFunction_t* out) {
+    std::lock_guard<std::mutex> g(g_jit_mtx);
+    auto it = g_jit_cache.find(src);
+    if (it != g_jit_cache.end()) {
+        *out = it->second.fn;
+        return 0;
+    }
+    if (g_jit_cache.size() >= 256) {
+        // bound module memory for workloads generating unbounded
+        // distinct programs; recompilation repopulates on demand.
+        // Drain the device first — a cached kernel may be in flight.
+        (void)hipDeviceSynchronize();
+        for (auto& kv : g_jit_cache) hipModuleUnload(kv.second.mod);
+        g_jit_cache.clear();
+    }
+    std::vector<char> code;
+    if (jit_compile(src, &code) != 0) return -1;
     JitEntry e;
     hipError_t he = hipModuleLoadData(&e.mod, code.data());
     if (he != hipSuccess) {
@@ -373,6 +479,66 @@ int launch_expr_jit(const int32_t* prog, int plen, void* dst,
     return 0;
 }
 
+// mirrored EXACTLY in the generated source (JRARGS_DECL)
+struct JRArgs {
+    JArgs a;
+    void* partials;
+    unsigned int* ticket;
+    void* out;
+    unsigned int base;
+    int fused;
+};
+
+// The caller (launch_expr_reduce) has validated the program, the layout
+// limits (strided: float, nd <= 4, n < 2^32) and sized st().partials.
+int launch_expr_reduce_jit(const int32_t* prog, int plen,
+                           const uint64_t* dims, int nd, void* const* srcs,
+                           const uint64_t* src_strides, int nsrcs,
+                           const double* consts, int nconsts, uint64_t n,
+                           int dtype, int redop, int g, bool fused,
+                           hipStream_t s) {
+    const char* e = getenv("DA_EXPR_JIT");
+    if (e && e[0] == '0') return 1;
+    if (g_jit_state < 0) return 1;   // earlier hard failure: interpreter
+    bool strided = src_strides != nullptr;
+    std::string src = gen_reduce_source(prog, plen, dtype, nd, nsrcs,
+                                        strided, redop);
+    hipFunction_t fn;
+    if (jit_get(src, &fn) != 0) {
+        g_jit_state = -1;
+        return 1;
+    }
+    g_jit_state = 2;
+
+    JRArgs r;
+    memset(&r, 0, sizeof(r));
+    for (int i = 0; i < nsrcs; ++i) r.a.srcs[i] = srcs[i];
+    for (int i = 0; i < nconsts; ++i) r.a.consts[i] = consts[i];
+    r.a.n = n;
+    if (strided) {
+        for (int d = 0; d < nd; ++d) r.a.dims[d] = (unsigned)dims[d];
+        for (int k = 0; k < nsrcs; ++k)
+            for (int d = 0; d < nd; ++d)
+                r.a.str[k][d] = (unsigned)src_strides[(size_t)k * nd + d];
+    }
+    r.partials = st().partials;
+    r.ticket = st().red_ticket;
+    r.out = st().red_host_dev;
+    r.fused = fused ? 1 : 0;
+    auto launch = [&](unsigned int base) {
+        r.base = base;
+        size_t rsz = sizeof(r);
+        void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &r,
+                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &rsz,
+                       HIP_LAUNCH_PARAM_END};
+        return hipModuleLaunchKernel(fn, (unsigned)g, 1, 1, 256, 1, 1, 0, s,
+                                     nullptr, cfg);
+    };
+    if (fused) return fanin_launch(g, launch);
+    DA_CHECK_HIP(launch(0u));
+    return 0;
+}
+
 int expr_jit_state() { return g_jit_state; }
 const char* expr_jit_err() { return g_jit_err; }
 
@@ -393,31 +559,28 @@ extern "C" int dbg_expr_jit_compile(const int32_t* prog, int plen,
         strncpy(src_out, src.c_str(), src_len - 1);
         src_out[src_len - 1] = 0;
     }
-    const char* hdr_names[] = {"stdint.h", "darray_hip.h", "mapops.hpp",
-                               "fastmath.hpp"};
-    const char* stdint_stub =
-        "#pragma once\n"
-        "typedef __INT8_TYPE__ int8_t;\ntypedef __UINT8_TYPE__ uint8_t;\n"
-        "typedef __INT16_TYPE__ int16_t;\ntypedef __UINT16_TYPE__ uint16_t;\n"
-        "typedef __INT32_TYPE__ int32_t;\ntypedef __UINT32_TYPE__ uint32_t;\n"
-        "typedef __INT64_TYPE__ int64_t;\ntypedef __UINT64_TYPE__ uint64_t;\n";
-    const char* hdrs[] = {stdint_stub, embedded_darray_hip_h,
-                          embedded_mapops_hpp, embedded_fastmath_hpp};
-    hiprtcProgram p;
-    if (hiprtcCreateProgram(&p, src.c_str(), "ejit.cu", 4, hdrs,
-                            hdr_names) != HIPRTC_SUCCESS)
+    return jit_compile(src, nullptr);
+}
+
+/* test-only sibling of dbg_expr_jit_compile for the fused mapreduce
+ * kernel: redop_or_count is a da_redop, or -1 for the count variant. */
+extern "C" int dbg_expr_reduce_jit_compile(const int32_t* prog, int plen,
+                                           int dtype, int nd, int nsrcs,
+                                           int strided, int redop_or_count,
+                                           char* src_out, int src_len) {
+    using namespace da;
+    if (validate_expr("dbg_expr_reduce_jit_compile", prog, plen, nsrcs,
+                      DA_EXPR_MAXCONSTS) != 0)
         return -1;
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17",
-                          "-ffp-contract=off"};
-    hiprtcResult rc = hiprtcCompileProgram(p, 4, opts);
-    if (rc != HIPRTC_SUCCESS) {
-        size_t lsz = 0;
-        hiprtcGetProgramLogSize(p, &lsz);
-        std::string log(lsz, 0);
-        if (lsz) hiprtcGetProgramLog(p, &log[0]);
-        snprintf(g_jit_err, sizeof(g_jit_err), "hiprtc compile: %.400s",
-                 log.c_str());
+    if (redop_or_count < DA_EXPR_COUNT || redop_or_count > DA_RED_MAX ||
+        nd < 1 || nd > DA_EXPR_MAXND ||
+        (dtype != DA_F64 && dtype != DA_F32 && dtype != DA_I64))
+        return -1;
+    std::string src = gen_reduce_source(prog, plen, dtype, nd, nsrcs,
+                                        strided != 0, redop_or_count);
+    if (src_out && src_len > 0) {
+        strncpy(src_out, src.c_str(), src_len - 1);
+        src_out[src_len - 1] = 0;
     }
-    hiprtcDestroyProgram(&p);
-    return rc == HIPRTC_SUCCESS ? 0 : -1;
+    return jit_compile(src, nullptr);
 }

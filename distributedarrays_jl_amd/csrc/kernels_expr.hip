@@ -28,6 +28,7 @@
 // Both HBM-bound; compiled -ffp-contract=off (Julia Base numerics).
 #include "common.hpp"
 #include "mapops.hpp"
+#include "reduce_core.hpp"
 #include <math.h>
 
 namespace da {
@@ -131,41 +132,47 @@ __global__ void expr_flat_kernel_i64(ExprProg p, int64_t* __restrict__ dst,
 // (stride 0 expands a singleton dim, the bclocal localisation of
 // broadcast.jl:140-152 after gather).
 template <typename T>
+__device__ __forceinline__ T expr_strided_eval(const ExprProg& p,
+                                               const ExprStrides& s,
+                                               uint64_t i) {
+    uint32_t idx[DA_EXPR_MAXND];
+    uint32_t rem = (uint32_t)i;   // local chunks are < 2^32 elements
+    for (int d = 0; d < s.nd; ++d) {
+        idx[d] = rem % s.dims[d];
+        rem /= s.dims[d];
+    }
+    uint64_t off[DA_EXPR_MAXARGS];
+    for (int a = 0; a < DA_EXPR_MAXARGS; ++a) off[a] = 0;
+    for (int d = 0; d < s.nd; ++d)
+        for (int a = 0; a < DA_EXPR_MAXARGS; ++a)
+            off[a] += (uint64_t)idx[d] * s.str[a][d];
+
+    T stack[DA_EXPR_MAXSTACK];
+    int sp = 0;
+    for (int pc = 0; pc < p.len; ++pc) {
+        int ins = p.ins[pc];
+        int kind = ins >> 8, opi = ins & 0xff;
+        switch (kind) {
+        case 1: stack[sp++] = ((const T*)p.srcs[opi])[off[opi]]; break;
+        case 2: stack[sp++] = (T)p.consts[opi]; break;
+        case 0: stack[sp - 1] = apply_map<T>(opi, stack[sp - 1]); break;
+        default: {
+            T b = stack[--sp];
+            stack[sp - 1] = apply_map2<T>(opi, stack[sp - 1], b);
+        }
+        }
+    }
+    return stack[0];
+}
+
+template <typename T>
 __device__ __forceinline__ void expr_strided_body(const ExprProg& p,
                                                   const ExprStrides& s,
                                                   T* dst, uint64_t n) {
     uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t gstride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = i0; i < n; i += gstride) {
-        uint32_t idx[DA_EXPR_MAXND];
-        uint32_t rem = (uint32_t)i;   // local chunks are < 2^32 elements
-        for (int d = 0; d < s.nd; ++d) {
-            idx[d] = rem % s.dims[d];
-            rem /= s.dims[d];
-        }
-        uint64_t off[DA_EXPR_MAXARGS];
-        for (int a = 0; a < DA_EXPR_MAXARGS; ++a) off[a] = 0;
-        for (int d = 0; d < s.nd; ++d)
-            for (int a = 0; a < DA_EXPR_MAXARGS; ++a)
-                off[a] += (uint64_t)idx[d] * s.str[a][d];
-
-        T stack[DA_EXPR_MAXSTACK];
-        int sp = 0;
-        for (int pc = 0; pc < p.len; ++pc) {
-            int ins = p.ins[pc];
-            int kind = ins >> 8, opi = ins & 0xff;
-            switch (kind) {
-            case 1: stack[sp++] = ((const T*)p.srcs[opi])[off[opi]]; break;
-            case 2: stack[sp++] = (T)p.consts[opi]; break;
-            case 0: stack[sp - 1] = apply_map<T>(opi, stack[sp - 1]); break;
-            default: {
-                T b = stack[--sp];
-                stack[sp - 1] = apply_map2<T>(opi, stack[sp - 1], b);
-            }
-            }
-        }
-        dst[i] = stack[0];
-    }
+    for (uint64_t i = i0; i < n; i += gstride)
+        dst[i] = expr_strided_eval<T>(p, s, i);
 }
 
 template <typename T>
@@ -174,43 +181,53 @@ __global__ void expr_strided_kernel(ExprProg p, ExprStrides s,
     expr_strided_body<T>(p, s, dst, n);
 }
 
-int launch_expr(const int32_t* prog, int plen, void* dst,
-                const uint64_t* dst_dims, int nd,
-                void* const* srcs, const uint64_t* src_strides, int nsrcs,
-                const double* consts, int nconsts,
-                uint64_t n, int dtype, hipStream_t s) {
+// Program validation shared by da_expr and da_expr_reduce / da_expr_count:
+// lengths, arg/const bounds and a host-side stack simulation.
+int validate_expr(const char* who, const int32_t* prog, int plen, int nsrcs,
+                  int nconsts) {
     if (plen <= 0 || plen > DA_EXPR_MAXLEN)
-        return set_err(-3, "da_expr: bad program length %d", plen);
+        return set_err(-3, "%s: bad program length %d", who, plen);
     if (nsrcs < 0 || nsrcs > DA_EXPR_MAXARGS || nconsts < 0 ||
         nconsts > DA_EXPR_MAXCONSTS)
-        return set_err(-3, "da_expr: too many args/consts");
+        return set_err(-3, "%s: too many args/consts", who);
     // host-side validation by stack simulation
     int sp = 0;
     for (int pc = 0; pc < plen; ++pc) {
         int kind = prog[pc] >> 8, idx = prog[pc] & 0xff;
         switch (kind) {
         case 1:
-            if (idx >= nsrcs) return set_err(-3, "da_expr: arg %d oob", idx);
+            if (idx >= nsrcs) return set_err(-3, "%s: arg %d oob", who, idx);
             ++sp; break;
         case 2:
             if (idx >= nconsts)
-                return set_err(-3, "da_expr: const %d oob", idx);
+                return set_err(-3, "%s: const %d oob", who, idx);
             ++sp; break;
         case 0:
             if (sp < 1 || idx >= DA_OP__N)
-                return set_err(-3, "da_expr: bad unary at %d", pc);
+                return set_err(-3, "%s: bad unary at %d", who, pc);
             break;
         case 3:
             if (sp < 2 || idx >= DA_OP2__N)
-                return set_err(-3, "da_expr: bad binary at %d", pc);
+                return set_err(-3, "%s: bad binary at %d", who, pc);
             --sp; break;
         default:
-            return set_err(-3, "da_expr: bad kind at %d", pc);
+            return set_err(-3, "%s: bad kind at %d", who, pc);
         }
         if (sp > DA_EXPR_MAXSTACK)
-            return set_err(-3, "da_expr: stack overflow at %d", pc);
+            return set_err(-3, "%s: stack overflow at %d", who, pc);
     }
-    if (sp != 1) return set_err(-3, "da_expr: program leaves %d values", sp);
+    if (sp != 1)
+        return set_err(-3, "%s: program leaves %d values", who, sp);
+    return 0;
+}
+
+int launch_expr(const int32_t* prog, int plen, void* dst,
+                const uint64_t* dst_dims, int nd,
+                void* const* srcs, const uint64_t* src_strides, int nsrcs,
+                const double* consts, int nconsts,
+                uint64_t n, int dtype, hipStream_t s) {
+    int vrc = validate_expr("da_expr", prog, plen, nsrcs, nconsts);
+    if (vrc) return vrc;
     if (n == 0) return 0;
 
     // preferred path: hipRTC-compiled kernel for this exact program
@@ -285,6 +302,184 @@ int launch_expr(const int32_t* prog, int plen, void* dst,
     }
     DA_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// ---- fused mapreduce over a program (da_expr_reduce / da_expr_count) --
+// The evaluators above feed the accumulate loop and fan-in of the flat
+// reduce (reduce_core.hpp) with the element-to-thread assignment and fold
+// order of da_reduce's kernels: thread i absorbs terms 2j, 2j+1 for
+// j = i, i+stride, ..., then the scalar tail; wave shuffle tree; 4-slot
+// LDS fold; the last arriver folds the block partials.  So the result
+// has the bits of materialising the program and reducing the temporary.
+// This interpreter form serves DA_EXPR_JIT=0 and hipRTC failures; the
+// generated kernels of expr_jit.hip run the same loop.
+template <typename T> struct ExprTerm {
+    static __device__ __forceinline__ T at(const ExprProg& p, uint64_t i) {
+        return expr_eval<T>(p, i);
+    }
+};
+template <> struct ExprTerm<int64_t> {
+    static __device__ __forceinline__ int64_t at(const ExprProg& p,
+                                                 uint64_t i) {
+        return expr_eval_i64(p, i);
+    }
+};
+
+// COUNT: +1 per nonzero term (a NaN is nonzero), in int64 whatever T
+template <bool COUNT, typename A, typename T>
+__device__ __forceinline__ A expr_absorb(int redop, A acc, T x) {
+    if constexpr (COUNT) return acc + (x != (T)0 ? 1 : 0);
+    else return red_comb(redop, acc, x);
+}
+
+// `partials` is not __restrict__/const: see reduce_fused
+template <typename T, typename A, bool COUNT, bool STRIDED>
+__global__ void expr_reduce_kernel(ExprProg p, ExprStrides s, uint64_t n,
+                                   int redop, A* partials,
+                                   unsigned int* ticket, unsigned int base,
+                                   int fused, A* out) {
+    __shared__ A sh[RTPB / 64 + 1];
+    auto term = [&](uint64_t i) -> T {
+        if constexpr (STRIDED) return expr_strided_eval<T>(p, s, i);
+        else return ExprTerm<T>::at(p, i);
+    };
+    if (COUNT) redop = DA_RED_ADD;
+    uint64_t i = (uint64_t)blockIdx.x * RTPB + threadIdx.x;
+    uint64_t stride = (uint64_t)gridDim.x * RTPB;
+    A acc = RedIdent<A>::get(redop);
+    uint64_t nv = n / 2;
+    for (uint64_t j = i; j < nv; j += stride) {
+        T r0 = term(2 * j);
+        T r1 = term(2 * j + 1);
+        acc = expr_absorb<COUNT>(redop, acc, r0);
+        acc = expr_absorb<COUNT>(redop, acc, r1);
+    }
+    for (uint64_t j = 2 * nv + i; j < n; j += stride)
+        acc = expr_absorb<COUNT>(redop, acc, term(j));
+    acc = block_reduce_in(redop, acc, sh);
+    if (fused)
+        fanin_finish(redop, acc, partials, ticket, base, out, sh);
+    else if (threadIdx.x == 0)
+        partials[blockIdx.x] = acc;
+}
+
+namespace {
+struct ExprRedArgs {
+    ExprProg P;
+    ExprStrides S;
+    uint64_t n;
+    int redop, g;
+    bool fused;
+    hipStream_t s;
+};
+
+template <typename T, typename A, bool COUNT, bool STRIDED>
+int expr_reduce_interp(const ExprRedArgs& a) {
+    A* parts = (A*)st().partials;
+    A* out = (A*)st().red_host_dev;
+    auto launch = [&](unsigned int base) {
+        hipLaunchKernelGGL((expr_reduce_kernel<T, A, COUNT, STRIDED>),
+                           dim3(a.g), dim3(RTPB), 0, a.s, a.P, a.S, a.n,
+                           a.redop, parts, st().red_ticket, base,
+                           a.fused ? 1 : 0, out);
+        return hipGetLastError();
+    };
+    if (a.fused) return fanin_launch(a.g, launch);
+    DA_CHECK_HIP(launch(0u));
+    return 0;
+}
+
+template <typename T, bool STRIDED>
+int expr_reduce_interp_t(const ExprRedArgs& a, bool count) {
+    return count ? expr_reduce_interp<T, int64_t, true, STRIDED>(a)
+                 : expr_reduce_interp<T, T, false, STRIDED>(a);
+}
+}  // namespace
+
+int launch_expr_reduce(const int32_t* prog, int plen, const uint64_t* dims,
+                       int nd, void* const* srcs,
+                       const uint64_t* src_strides, int nsrcs,
+                       const double* consts, int nconsts, uint64_t n,
+                       int dtype, int redop, void* out_host, hipStream_t s) {
+    const bool count = redop == DA_EXPR_COUNT;
+    const char* who = count ? "da_expr_count" : "da_expr_reduce";
+    int rc = validate_expr(who, prog, plen, nsrcs, nconsts);
+    if (rc) return rc;
+    if (!count && (redop < 0 || redop > DA_RED_MAX))
+        return set_err(-3, "%s: bad redop %d", who, redop);
+    if (!out_host) return set_err(-3, "%s: null out", who);
+    if (dtype != DA_F64 && dtype != DA_F32 && dtype != DA_I64)
+        return set_err(-3, "%s: bad dtype %d", who, dtype);
+    if (nsrcs > 0 && !srcs) return set_err(-3, "%s: null srcs", who);
+    const bool strided = src_strides != nullptr;
+    if (strided) {
+        if (dtype == DA_I64)
+            return set_err(-3, "%s: strided variant is float-only", who);
+        if (nd < 1 || nd > DA_EXPR_MAXND || !dims)
+            return set_err(-3, "%s: nd %d unsupported (max %d)", who, nd,
+                           DA_EXPR_MAXND);
+        if (n >> 32)
+            return set_err(-3, "%s: strided variant needs n < 2^32", who);
+        uint64_t total = 1;
+        for (int d = 0; d < nd; ++d) total *= dims[d];
+        if (total != n) return set_err(-3, "%s: dims/numel mismatch", who);
+    }
+    if (n == 0) {  // fold identity / zero count, no launch
+        if (count) *(int64_t*)out_host = 0;
+        else if (dtype == DA_F64)
+            *(double*)out_host = RedIdent<double>::get(redop);
+        else if (dtype == DA_F32)
+            *(float*)out_host = RedIdent<float>::get(redop);
+        else *(int64_t*)out_host = RedIdent<int64_t>::get(redop);
+        return 0;
+    }
+    // da_reduce's grid for n elements, whatever the program or layout
+    const int g = reduce_grid((n / 2 + RTPB - 1) / RTPB);
+    rc = ensure_partials(RMAXB * sizeof(double));
+    if (rc) return rc;
+    const bool fused = reduce_fused_on();
+
+    rc = launch_expr_reduce_jit(prog, plen, dims, nd, srcs, src_strides,
+                                nsrcs, consts, nconsts, n, dtype, redop, g,
+                                fused, s);
+    if (rc < 0) return rc;
+    if (rc == 1) {   // interpreter (DA_EXPR_JIT=0 or hipRTC failed)
+        ExprRedArgs a;
+        memset(&a, 0, sizeof(a));
+        for (int i = 0; i < plen; ++i) a.P.ins[i] = prog[i];
+        a.P.len = plen;
+        for (int i = 0; i < nsrcs; ++i) a.P.srcs[i] = srcs[i];
+        for (int i = 0; i < nconsts; ++i) a.P.consts[i] = consts[i];
+        if (strided) {
+            a.S.nd = nd;
+            for (int d = 0; d < nd; ++d) a.S.dims[d] = (uint32_t)dims[d];
+            for (int k = 0; k < nsrcs; ++k)
+                for (int d = 0; d < nd; ++d)
+                    a.S.str[k][d] =
+                        (uint32_t)src_strides[(size_t)k * nd + d];
+        }
+        a.n = n;
+        a.redop = redop;
+        a.g = g;
+        a.fused = fused;
+        a.s = s;
+        if (dtype == DA_I64)
+            rc = expr_reduce_interp_t<int64_t, false>(a, count);
+        else if (dtype == DA_F64)
+            rc = strided ? expr_reduce_interp_t<double, true>(a, count)
+                         : expr_reduce_interp_t<double, false>(a, count);
+        else
+            rc = strided ? expr_reduce_interp_t<float, true>(a, count)
+                         : expr_reduce_interp_t<float, false>(a, count);
+        if (rc) return rc;
+    }
+    if (!fused) {
+        rc = reduce_stage2_launch(count ? (int)DA_RED_ADD : redop, g,
+                                  count ? (int)DA_I64 : dtype, s);
+        if (rc) return rc;
+    }
+    return reduce_result(out_host, count ? sizeof(int64_t)
+                                         : dtype_size(dtype), s);
 }
 
 } // namespace da

@@ -12,14 +12,14 @@
 // a tree, within the 1e-6 contract of BASELINE.json (the reference's own
 // fold order is likewise unspecified: docs/src/index.md:208-236).
 #include "common.hpp"
+#include "reduce_core.hpp"
 #include <stdlib.h>
 
 namespace da {
 
-constexpr int RTPB = 256;          // 4 waves per block
-constexpr int RMAXB = 8192;        // block partials (fits scratch)
-
-static inline int reduce_grid(uint64_t want) {
+// reduce_grid: blocks of a flat reduce over `want` blocks' worth of work,
+// capped (DA_RBLOCKS, default 2048).
+int reduce_grid(uint64_t want) {
     static int cap = -1;
     if (cap < 0) {
         const char* e = getenv("DA_RBLOCKS");
@@ -37,51 +37,6 @@ static inline bool reduce_v4() {
         v = e ? atoi(e) : 0;
     }
     return v == 1;
-}
-
-template <typename T> struct RedIdent {
-    static __device__ __host__ T get(int redop) {
-        switch (redop) {
-        case DA_RED_ADD: return (T)0;
-        case DA_RED_MUL: return (T)1;
-        case DA_RED_MIN: return (T)INFINITY;
-        case DA_RED_MAX: return (T)(-INFINITY);
-        }
-        return (T)0;
-    }
-};
-template <> struct RedIdent<int64_t> {
-    static __device__ __host__ int64_t get(int redop) {
-        switch (redop) {
-        case DA_RED_ADD: return 0;
-        case DA_RED_MUL: return 1;
-        case DA_RED_MIN: return INT64_MAX;
-        case DA_RED_MAX: return INT64_MIN;
-        }
-        return 0;
-    }
-};
-
-template <typename T>
-__device__ __forceinline__ T red_comb(int redop, T a, T b) {
-    switch (redop) {
-    case DA_RED_ADD: return a + b;
-    case DA_RED_MUL: return a * b;
-    case DA_RED_MIN:  // NaN-propagating (Julia min)
-        return a != a ? a : (b != b ? b : (a < b ? a : b));
-    case DA_RED_MAX:
-        return a != a ? a : (b != b ? b : (a > b ? a : b));
-    }
-    return a;
-}
-__device__ __forceinline__ int64_t red_comb(int redop, int64_t a, int64_t b) {
-    switch (redop) {
-    case DA_RED_ADD: return (int64_t)((uint64_t)a + (uint64_t)b);
-    case DA_RED_MUL: return (int64_t)((uint64_t)a * (uint64_t)b);
-    case DA_RED_MIN: return a < b ? a : b;
-    case DA_RED_MAX: return a > b ? a : b;
-    }
-    return a;
 }
 
 template <typename T>
@@ -106,26 +61,6 @@ __device__ __forceinline__ int64_t mapf(int mapop, int64_t x) {
     case DA_REDF_NONZERO: return x != 0 ? 1 : 0;
     }
     return x;
-}
-
-// `lds`: RTPB/64 workgroup-shared elements, one per wave.
-template <typename T>
-__device__ __forceinline__ T block_reduce_in(int redop, T v, T* lds) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = red_comb(redop, v, (T)__shfl_down(v, off, 64));
-    int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    if (lane == 0) lds[wave] = v;
-    __syncthreads();
-    if (wave == 0) {
-        T w = lane < (RTPB / 64) ? lds[lane]
-                                 : RedIdent<T>::get(redop);
-#pragma unroll
-        for (int off = 2; off > 0; off >>= 1)
-            w = red_comb(redop, w, (T)__shfl_down(w, off, 64));
-        return w;
-    }
-    return v;
 }
 
 template <typename T>
@@ -183,68 +118,9 @@ __global__ void reduce_stage1_v4(int mapop, int redop,
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
-// ---- single-launch fan-in (cdna_hip_programming.md §5, "In-launch
-// split-K reduction", in its fence-free form; §6 Guideline 16 R1).
-// Each block's payload is ONE partial of <= 8 bytes, so it is published
-// by a relaxed agent-scope atomic store — a write-through (sc1) store
-// that needs no release fence — drained by the storing wave's
-// s_waitcnt vmcnt(0) before that same lane takes its ticket.  Only the
-// last arriver pays a fence: one agent-scope acquire, then plain loads
-// of all partials in reduce_stage2's fold order (thread t folds
-// t, t+256, ...; then block_reduce), so both paths give the same bits.
-// No block waits for another, so residency is irrelevant.
+// The single-launch fan-in (publish_partial, fanin_finish) and its
+// ticket invariant are in reduce_core.hpp.
 //
-// Ticket invariant: the counter is zeroed once in da_init and never
-// reset.  Every launch of g blocks adds exactly g, and launches of the
-// one library stream run in order, so before a launch the counter
-// equals State::red_base (mod 2^32), which the host advances by g per
-// launch.  A block is last iff ticket - base == g - 1 in unsigned
-// arithmetic; that holds across wrap-around, any sequence of grid
-// sizes, and interleaved dtypes / reduce / count calls.
-template <typename A>
-__device__ __forceinline__ void publish_partial(A* p, A v) {
-    if constexpr (sizeof(A) == 8)
-        __hip_atomic_store((unsigned long long*)p,
-                           __builtin_bit_cast(unsigned long long, v),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        __hip_atomic_store((unsigned int*)p,
-                           __builtin_bit_cast(unsigned int, v),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// `acc`: the block's partial (valid in thread 0).  `sh`: RTPB/64 + 1
-// shared elements — block_reduce_in's scratch plus the "I am last"
-// flag, kept in ONE __shared__ object.  Reusing sh[0..3] for the final
-// fold is safe: wave 0 read them before it wrote the flag, and every
-// other wave writes them again only after the barriers below.
-template <typename A>
-__device__ __forceinline__ void fanin_finish(int redop, A acc, A* partials,
-                                             unsigned int* ticket,
-                                             unsigned int base, A* out,
-                                             A* sh) {
-    if (threadIdx.x == 0) {
-        publish_partial(partials + blockIdx.x, acc);
-        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned int t = __hip_atomic_fetch_add(
-            ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sh[RTPB / 64] = (t - base == gridDim.x - 1) ? (A)1 : (A)0;
-    }
-    __syncthreads();
-    if (sh[RTPB / 64] == (A)0) return;
-    // guide order: the fence, that lane's vmcnt wait, the barrier
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    A facc = RedIdent<A>::get(redop);
-    for (unsigned int j = threadIdx.x; j < gridDim.x; j += RTPB)
-        facc = red_comb(redop, facc, partials[j]);
-    facc = block_reduce_in(redop, facc, sh);
-    if (threadIdx.x == 0) out[0] = facc;
-}
-
 // `partials` is deliberately not __restrict__/const: its loads must stay
 // vector loads behind the acquire.  `out` is host-visible pinned memory.
 template <typename T, int MOP = -1, int ROP = -1>
@@ -271,7 +147,7 @@ __global__ void reduce_stage2(int redop, const T* __restrict__ partials,
 }
 
 // DA_RED_FUSED: unset or nonzero = single launch; 0 = stage 1 + stage 2.
-static inline bool reduce_fused_on() {
+bool reduce_fused_on() {
     static int v = -1;
     if (v < 0) {
         const char* e = getenv("DA_RED_FUSED");
@@ -290,15 +166,19 @@ template <typename T> struct FlatArgs {
 };
 
 template <typename T, int MOP, int ROP>
-static void launch_flat(const FlatArgs<T>& a) {
+static int launch_flat(const FlatArgs<T>& a) {
     if (a.fused)
-        hipLaunchKernelGGL((reduce_fused<T, MOP, ROP>), dim3(a.grid),
-                           dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src, a.n,
-                           a.parts, st().red_ticket, st().red_base, a.out);
-    else
-        hipLaunchKernelGGL((reduce_stage1<T, MOP, ROP>), dim3(a.grid),
-                           dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src, a.n,
-                           a.parts);
+        return fanin_launch(a.grid, [&](unsigned int base) {
+            hipLaunchKernelGGL((reduce_fused<T, MOP, ROP>), dim3(a.grid),
+                               dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src,
+                               a.n, a.parts, st().red_ticket, base, a.out);
+            return hipGetLastError();
+        });
+    hipLaunchKernelGGL((reduce_stage1<T, MOP, ROP>), dim3(a.grid),
+                       dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src, a.n,
+                       a.parts);
+    DA_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 template <typename T>
@@ -313,36 +193,31 @@ static int do_reduce(int mapop, int redop, const T* src, uint64_t n,
     int g = reduce_grid(want);
     int rc = ensure_partials(RMAXB * sizeof(double));
     if (rc) return rc;
-    // the result lands in the pinned host slot: no device-to-host copy
-    // command follows the kernels
     FlatArgs<T> a = {reduce_fused_on() && !v4, g, mapop, redop, src, n,
                      (T*)st().partials, (T*)st().red_host_dev, s};
-    if (v4)
+    if (v4) {
         hipLaunchKernelGGL((reduce_stage1_v4<T>), dim3(g), dim3(RTPB),
                            0, s, mapop, redop, src, n, a.parts);
-    else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_ADD)
-        launch_flat<T, DA_REDF_IDENTITY, DA_RED_ADD>(a);
+        DA_CHECK_HIP(hipGetLastError());
+    } else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_ADD)
+        rc = launch_flat<T, DA_REDF_IDENTITY, DA_RED_ADD>(a);
     else if (mapop == DA_REDF_ABS2 && redop == DA_RED_ADD)
-        launch_flat<T, DA_REDF_ABS2, DA_RED_ADD>(a);
+        rc = launch_flat<T, DA_REDF_ABS2, DA_RED_ADD>(a);
     else if (mapop == DA_REDF_ABS && redop == DA_RED_ADD)
-        launch_flat<T, DA_REDF_ABS, DA_RED_ADD>(a);
+        rc = launch_flat<T, DA_REDF_ABS, DA_RED_ADD>(a);
     else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_MAX)
-        launch_flat<T, DA_REDF_IDENTITY, DA_RED_MAX>(a);
+        rc = launch_flat<T, DA_REDF_IDENTITY, DA_RED_MAX>(a);
     else if (mapop == DA_REDF_IDENTITY && redop == DA_RED_MIN)
-        launch_flat<T, DA_REDF_IDENTITY, DA_RED_MIN>(a);
+        rc = launch_flat<T, DA_REDF_IDENTITY, DA_RED_MIN>(a);
     else
-        launch_flat<T, -1, -1>(a);
-    DA_CHECK_HIP(hipGetLastError());
-    if (a.fused) {
-        st().red_base += (unsigned int)g;
-    } else {
+        rc = launch_flat<T, -1, -1>(a);
+    if (rc) return rc;
+    if (!a.fused) {
         hipLaunchKernelGGL(reduce_stage2<T>, dim3(1), dim3(RTPB), 0, s,
                            redop, a.parts, g, a.out);
         DA_CHECK_HIP(hipGetLastError());
     }
-    DA_CHECK_HIP(hipStreamSynchronize(s));
-    memcpy(out_host, st().red_host, sizeof(T));
-    return 0;
+    return reduce_result(out_host, sizeof(T), s);
 }
 
 // Exact predicate count: the 0/1 predicate of a T source is accumulated
@@ -392,11 +267,13 @@ static int do_count(int mapop, const T* src, uint64_t n, int64_t* out_host,
     int64_t* parts = (int64_t*)st().partials;
     int64_t* out = (int64_t*)st().red_host_dev;
     if (reduce_fused_on()) {
-        hipLaunchKernelGGL(count_fused<T>, dim3(g), dim3(RTPB), 0, s,
-                           mapop, src, n, parts, st().red_ticket,
-                           st().red_base, out);
-        DA_CHECK_HIP(hipGetLastError());
-        st().red_base += (unsigned int)g;
+        rc = fanin_launch(g, [&](unsigned int base) {
+            hipLaunchKernelGGL(count_fused<T>, dim3(g), dim3(RTPB), 0, s,
+                               mapop, src, n, parts, st().red_ticket, base,
+                               out);
+            return hipGetLastError();
+        });
+        if (rc) return rc;
     } else {
         hipLaunchKernelGGL(count_stage1<T>, dim3(g), dim3(RTPB), 0, s,
                            mapop, src, n, parts);
@@ -405,9 +282,7 @@ static int do_count(int mapop, const T* src, uint64_t n, int64_t* out_host,
                            (int)DA_RED_ADD, parts, g, out);
         DA_CHECK_HIP(hipGetLastError());
     }
-    DA_CHECK_HIP(hipStreamSynchronize(s));
-    memcpy(out_host, st().red_host, sizeof(int64_t));
-    return 0;
+    return reduce_result(out_host, sizeof(int64_t), s);
 }
 
 int launch_count(int mapop, const void* src, uint64_t n, int dtype,
@@ -669,6 +544,38 @@ int launch_reduce(int mapop, int redop, const void* src, uint64_t n,
                                            n, out_host, s);
     }
     return set_err(-3, "da_reduce: bad dtype %d", dtype);
+}
+
+// reduce_stage2 for callers outside this file (the expression reduce under
+// DA_RED_FUSED=0): one block folds the g partials of `dtype` in
+// st().partials into the pinned slot.
+int reduce_stage2_launch(int redop, int g, int dtype, hipStream_t s) {
+    switch (dtype) {
+    case DA_F64:
+        hipLaunchKernelGGL(reduce_stage2<double>, dim3(1), dim3(RTPB), 0, s,
+                           redop, (const double*)st().partials, g,
+                           (double*)st().red_host_dev);
+        break;
+    case DA_F32:
+        hipLaunchKernelGGL(reduce_stage2<float>, dim3(1), dim3(RTPB), 0, s,
+                           redop, (const float*)st().partials, g,
+                           (float*)st().red_host_dev);
+        break;
+    default:
+        hipLaunchKernelGGL(reduce_stage2<int64_t>, dim3(1), dim3(RTPB), 0, s,
+                           redop, (const int64_t*)st().partials, g,
+                           (int64_t*)st().red_host_dev);
+    }
+    DA_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The result is in the pinned host slot once the stream has drained: no
+// device-to-host copy command follows the kernels.
+int reduce_result(void* out_host, size_t bytes, hipStream_t s) {
+    DA_CHECK_HIP(hipStreamSynchronize(s));
+    memcpy(out_host, st().red_host, bytes);
+    return 0;
 }
 
 } // namespace da

@@ -13,6 +13,8 @@ Usage (mirrors `D .= A .- M .* sin.(C)`):
     e = E.ref(A) - E.ref(M) * E.sin(E.ref(C))
     E.materialize_(D, e)        # in-place (Base.materialize!)
     G = E.materialize(e)        # allocating (Base.materialize / copy)
+    s = E.reduce("add", e)      # mapreduce over the tree, nothing stored
+    k = E.count(e)              # exact number of nonzero values
 
 Numerics: da_expr shares the scalar functor tables with da_map/da_map2
 (csrc/mapops.hpp), so a fused chain is bit-identical to the equivalent
@@ -20,7 +22,7 @@ sequence of single-op kernels."""
 import ctypes
 
 from ._ffi import check, lib, DArrayError
-from ._opcodes import (DTYPES, MAP_OP, MAP2_OP,
+from ._opcodes import (DTYPES, MAP_OP, MAP2_OP, RED_OPS,
                        I64_MAP_OPS, I64_MAP2_OPS)
 
 K_UNARY, K_ARG, K_CONST, K_BINARY = 0, 1, 2, 3
@@ -232,18 +234,17 @@ def _validate(dest, prog, args, consts):
                                   "representable" % c)
 
 
-def materialize_(dest, e):
-    """Base.materialize!(dest, bc) — copyto!(::DArray, ::Broadcasted)
-    (broadcast.jl:65-85).  Collective: every rank passes the same tree
-    (metadata-deterministic branches)."""
+def _localize(dest, args):
+    """Per-operand localisation onto dest's chunk boxes (bclocal /
+    makelocal, broadcast.jl:140-152 + _bcview :103-120), shared by
+    materialize_ and the fused reductions.  `dest` only supplies
+    geometry (dims, idxs, ranks, lshape).  An operand with dest's exact
+    layout contributes its own chunk pointer; any other is projected
+    through gather_box (singleton dims clamp to (0, 1) and get stride 0).
+    Returns (flat, ptrs, strides, bufs); the caller frees bufs."""
     from .ops import gather_box, _same_layout
 
-    prog, args, consts = compile_expr(e)
-    _validate(dest, prog, args, consts)
     nd = dest.ndims
-    if nd > MAXND:
-        raise DArrayError("expr: ndims %d > %d" % (nd, MAXND))
-
     full = [a.dims == dest.dims for a in args]
     aligned = [full[i] and _same_layout(dest, a)
                for i, a in enumerate(args)]
@@ -255,8 +256,6 @@ def materialize_(dest, e):
     bufs = [None] * len(args)
     ptrs = [None] * len(args)
     strides = [None] * len(args)
-    # destination-box projection per operand (bclocal: singleton dims
-    # clamp to (0, 1), broadcast.jl:140-152 + _bcview :103-120)
     for i, a in enumerate(args):
         if aligned[i]:
             ptrs[i] = a._ptr()
@@ -280,25 +279,47 @@ def materialize_(dest, e):
                 ss.append(t if a.dims[d] != 1 else 0)
                 t *= bshape[d]
             strides[i] = ss
+    return flat, ptrs, strides, bufs
+
+
+def _program_args(dest, prog, consts, flat, ptrs, strides):
+    """ctypes arrays of the program arguments common to da_expr,
+    da_expr_reduce and da_expr_count."""
+    nd = dest.ndims
+    parr = (ctypes.c_int32 * len(prog))(*prog)
+    dims_arr = (ctypes.c_uint64 * max(nd, 1))(*dest.lshape)
+    src_arr = (ctypes.c_void_p * max(len(ptrs), 1))(
+        *[p.value if p is not None else 0 for p in ptrs])
+    cons_arr = (ctypes.c_double * max(len(consts), 1))(*consts)
+    if flat:
+        sarr = None
+    else:
+        flat_strides = []
+        for ss in strides:
+            flat_strides.extend(ss if ss is not None else [0] * nd)
+        sarr = (ctypes.c_uint64 * max(len(flat_strides), 1))(
+            *flat_strides)
+    return parr, dims_arr, src_arr, sarr, cons_arr
+
+
+def materialize_(dest, e):
+    """Base.materialize!(dest, bc) — copyto!(::DArray, ::Broadcasted)
+    (broadcast.jl:65-85).  Collective: every rank passes the same tree
+    (metadata-deterministic branches)."""
+    prog, args, consts = compile_expr(e)
+    _validate(dest, prog, args, consts)
+    nd = dest.ndims
+    if nd > MAXND:
+        raise DArrayError("expr: ndims %d > %d" % (nd, MAXND))
+
+    flat, ptrs, strides, bufs = _localize(dest, args)
 
     if dest.lnumel:
-        n = dest.lnumel
-        parr = (ctypes.c_int32 * len(prog))(*prog)
-        dims_arr = (ctypes.c_uint64 * max(nd, 1))(*dest.lshape)
-        src_arr = (ctypes.c_void_p * max(len(args), 1))(
-            *[p.value if p is not None else 0 for p in ptrs])
-        cons_arr = (ctypes.c_double * max(len(consts), 1))(*consts)
-        if flat:
-            sarr = None
-        else:
-            flat_strides = []
-            for ss in strides:
-                flat_strides.extend(ss if ss is not None else [0] * nd)
-            sarr = (ctypes.c_uint64 * max(len(flat_strides), 1))(
-                *flat_strides)
+        parr, dims_arr, src_arr, sarr, cons_arr = _program_args(
+            dest, prog, consts, flat, ptrs, strides)
         check(lib.da_expr(parr, len(prog), dest._ptr(), dims_arr, nd,
                           src_arr, sarr, len(args), cons_arr,
-                          len(consts), n, DTYPES[dest.dtype]))
+                          len(consts), dest.lnumel, DTYPES[dest.dtype]))
     if any(b is not None for b in bufs):
         check(lib.da_synchronize())
     for b in bufs:
@@ -307,20 +328,25 @@ def materialize_(dest, e):
     return dest
 
 
+def _domain(args):
+    """(broadcast shape of the operands, first full-shape operand or
+    None)."""
+    if not args:
+        raise DArrayError("expr: no DArray operands")
+    dims = tuple(max(a.dims[d] for a in args)
+                 for d in range(args[0].ndims))
+    for a in args:
+        if a.dims == dims:
+            return dims, a
+    return dims, None
+
+
 def materialize(e):
     """Base.materialize(bc) — `copy(bc)` (broadcast.jl:91-98): allocate
     the result with the layout of the first full-shape operand (the
     `similar` overload, broadcast.jl:44-50)."""
     prog, args, consts = compile_expr(e)
-    if not args:
-        raise DArrayError("expr: no DArray operands")
-    dims = tuple(max(a.dims[d] for a in args)
-                 for d in range(args[0].ndims))
-    proto = None
-    for a in args:
-        if a.dims == dims:
-            proto = a
-            break
+    dims, proto = _domain(args)
     if proto is not None:
         dest = proto.similar()
     else:
@@ -330,3 +356,74 @@ def materialize(e):
         from .darray import DArray
         dest = DArray(dims, args[0].dtype)
     return materialize_(dest, e)
+
+
+# ------------------------------------------------------ fused reductions
+_CTYPE = {"f64": ctypes.c_double, "f32": ctypes.c_float,
+          "i64": ctypes.c_int64}
+
+
+def _fused(e, op):
+    """Local da_expr_reduce (op a fold name) / da_expr_count (op None)
+    over this rank's chunk of the broadcast domain, then the cross-rank
+    fold.  The chunk layout is that of the first full-shape operand (the
+    rule of materialize); with none (row .+ column) it is the default
+    grid for the broadcast shape — geometry only, nothing is allocated."""
+    prog, args, consts = compile_expr(e)
+    dims, dom = _domain(args)
+    if dom is None:
+        from .darray import DArray
+        dom = DArray(dims, args[0].dtype, _alloc=False)
+    _validate(dom, prog, args, consts)
+    nd = dom.ndims
+    if nd > MAXND:
+        raise DArrayError("expr: ndims %d > %d" % (nd, MAXND))
+
+    flat, ptrs, strides, bufs = _localize(dom, args)
+    try:
+        parr, dims_arr, src_arr, sarr, cons_arr = _program_args(
+            dom, prog, consts, flat, ptrs, strides)
+        # an empty chunk still calls in: n == 0 returns the fold
+        # identity / zero without a launch
+        if op is None:
+            out, rdtype, rop = ctypes.c_int64(), "i64", "add"
+            check(lib.da_expr_count(parr, len(prog), dims_arr, nd, src_arr,
+                                    sarr, len(args), cons_arr, len(consts),
+                                    dom.lnumel, DTYPES[dom.dtype],
+                                    ctypes.byref(out)))
+        else:
+            out, rdtype, rop = _CTYPE[dom.dtype](), dom.dtype, op
+            check(lib.da_expr_reduce(parr, len(prog), dims_arr, nd, src_arr,
+                                     sarr, len(args), cons_arr, len(consts),
+                                     dom.lnumel, DTYPES[dom.dtype],
+                                     RED_OPS[op], ctypes.byref(out)))
+    finally:
+        for b in bufs:
+            if b is not None:
+                b.free()
+    if dom.nranks > 1:
+        check(lib.da_allreduce(ctypes.byref(out), 1, DTYPES[rdtype],
+                               RED_OPS[rop]))
+    return out.value
+
+
+def reduce(op, e):
+    """mapreduce(f, op, A...) with f given as a broadcast tree
+    (mapreduce.jl:29-35), fused: every operand element is read once and
+    nothing is materialised.  op is add, mul, min or max; returns a
+    Python scalar.  Collective.  The result has exactly the bits of
+    mapreduce("identity", op, materialize(e)).
+
+        E.reduce("add", E.ref(x) * E.ref(y))          # dot, one pass
+        E.reduce("add", E.abs2(E.ref(a) - E.ref(b)))  # sum(abs2, a .- b)
+    """
+    if op not in RED_OPS:
+        raise DArrayError("expr: unknown reduction %r" % (op,))
+    return _fused(wrap(e), op)
+
+
+def count(e):
+    """count(!iszero, bc): the exact number of nonzero elements of the
+    tree's values (a NaN counts), as an int.  Predicates are composed
+    from the op tables, e.g. x > c as sign(max2(x - c, 0)).  Collective."""
+    return int(_fused(wrap(e), None))

@@ -233,10 +233,32 @@ def _local_reduce(f, op, d):
     return out
 
 
-def mapreduce(f, op, d):
+def _tree(f, ds):
+    """The broadcast tree a callable builds from E.ref of each array."""
+    from . import expr as E
+    e = f(*[E.ref(a) for a in ds])
+    if not isinstance(e, E.Expr):
+        raise DArrayError("a callable f must return an expression built "
+                          "from its arguments (expr.Expr), got %r"
+                          % type(e))
+    return e
+
+
+def mapreduce(f, op, d, *more):
     """mapreduce(f, op, d) — mapreduce.jl:29-35: per-chunk kernel
     reduction, then the cross-worker fold as one scalar RCCL allreduce
-    (tree; partials are 8 bytes — latency-bound)."""
+    (tree; partials are 8 bytes — latency-bound).
+
+    f is a name from RED_FS, or a callable: it is called with expr.ref
+    of each array and returns a broadcast tree, which is reduced fused
+    (expr.reduce: one pass, no temporary) — mapreduce(t -> t*t, +, D)
+    is mapreduce(lambda t: t * t, "add", D), and Julia's multi-array
+    mapreduce(f, op, A, B) passes the further arrays after d."""
+    if callable(f):
+        from . import expr as E
+        return E.reduce(op, _tree(f, (d,) + more))
+    if more:
+        raise DArrayError("mapreduce: several arrays need a callable f")
     out = _local_reduce(f, op, d)
     if d.nranks > 1:
         check(lib.da_allreduce(ctypes.byref(out), 1, DTYPES[d.dtype],
@@ -274,11 +296,35 @@ def dmean(d):
     return dsum(d) / d.size
 
 
+def dvar(d, corrected=True):
+    """var(d; corrected) (Statistics.var): two passes, no temporary —
+    the mean, then the fused sum(abs2, d .- mean)."""
+    if d.dtype == "i64":
+        raise DArrayError("dvar: float arrays only (dcast first)")
+    if d.size == 0:
+        return float("nan")
+    from . import expr as E
+    m = dmean(d)
+    ss = E.reduce("add", E.abs2(E.ref(d) - m))
+    den = d.size - 1 if corrected else d.size
+    return ss / den if den > 0 else float("nan")
+
+
+def dstd(d, corrected=True):
+    """std(d; corrected): sqrt of dvar."""
+    return float(np.sqrt(dvar(d, corrected)))
+
+
 def dcount(pred, d):
     """count(f, A) — mapreduce.jl:115-122 (pred in {nonzero, isnan,
     isfinite}).  Exact for every dtype and size: the predicate is
     counted in a 64-bit integer on the device (da_count) and folded
-    across ranks as i64 — a float accumulator rounds above 2^24."""
+    across ranks as i64 — a float accumulator rounds above 2^24.
+    A callable pred builds a broadcast tree (as in mapreduce) whose
+    nonzero values are counted fused (expr.count)."""
+    if callable(pred):
+        from . import expr as E
+        return E.count(_tree(pred, (d,)))
     if pred not in _PREDICATES:
         raise DArrayError("dcount: %r is not a predicate" % (pred,))
     out = ctypes.c_int64()
@@ -291,16 +337,20 @@ def dcount(pred, d):
 
 
 def dall(pred, d):
-    """all(f, A) — mapreduce.jl:97-104."""
+    """all(f, A) — mapreduce.jl:97-104 (callable f: count == size)."""
     if d.size == 0:
         return True
+    if callable(pred):
+        return dcount(pred, d) == d.size
     return mapreduce(pred, "min", d) == 1
 
 
 def dany(pred, d):
-    """any(f, A) — mapreduce.jl:106-113."""
+    """any(f, A) — mapreduce.jl:106-113 (callable f: count > 0)."""
     if d.size == 0:
         return False
+    if callable(pred):
+        return dcount(pred, d) > 0
     return mapreduce(pred, "max", d) == 1
 
 

@@ -185,6 +185,28 @@ int da_expr(const int32_t* prog, int prog_len, void* dst,
  * state: 1 ready, 2 active, -1 hipRTC failed (interpreter fallback). */
 int da_expr_jit_state(void);
 const char* da_expr_jit_errstr(void);
+/* Fused mapreduce over a program: op-folds (da_expr_reduce) or counts the
+ * nonzero terms of (da_expr_count; exact, NaN counts) the program's values
+ * over a local chunk of n elements WITHOUT materialising them — one
+ * launch, one read per operand element, result in *out (host; the dtype's
+ * own scalar / an int64_t).  Program arguments as da_expr; dims is the
+ * local chunk shape reduced over; src_strides == NULL means every operand
+ * is dense over it (f64/f32/i64, any n), else the strided variant
+ * (f64/f32, nd <= 4, n < 2^32).  n == 0 gives the fold identity / 0.
+ * Fold-order contract: *out has EXACTLY the bits of da_expr into a dense
+ * temporary followed by da_reduce(DA_REDF_IDENTITY, redop, tmp, n) /
+ * da_count(DA_REDF_NONZERO, tmp, n) in the same process (DA_RV4 does not
+ * apply; DA_RED_FUSED=0 and DA_EXPR_JIT=0 are honoured, same bits). */
+int da_expr_reduce(const int32_t* prog, int prog_len,
+                   const uint64_t* dims, int nd,
+                   void* const* srcs, const uint64_t* src_strides, int nsrcs,
+                   const double* consts, int nconsts, uint64_t n, int dtype,
+                   int redop, void* out);
+int da_expr_count(const int32_t* prog, int prog_len,
+                  const uint64_t* dims, int nd,
+                  void* const* srcs, const uint64_t* src_strides, int nsrcs,
+                  const double* consts, int nconsts, uint64_t n, int dtype,
+                  int64_t* out);
 int da_map2_scalar(int opcode, void* dst, const void* src, double c,
                    int reverse, uint64_t n, int dtype);      /* D .+ 1 etc (scalar broadcast arg, broadcast.jl:124-133) */
 int da_axpby(void* y, const void* x, double alpha, double beta,
