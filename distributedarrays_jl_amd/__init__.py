@@ -31,7 +31,8 @@ from .ops import (map_, dmap, map2_, elementwise, map2_scalar_, elementwise_scal
                   map2_general,
                   broadcast_fma_general, dsort, dtranspose, ddiag_lmul, ddiag_rmul,
                   dgetindex, dmul_, gather_sel, dgetindex_sel, dsub,
-                  dsetindex_)
+                  dsetindex_, daccumulate, daccumulate_, dcumsum, dcumprod,
+                  dcummax, dcummin)
 
 __all__ = [
     "DArray", "DArrayError", "comm", "geometry", "plan", "spmd", "expr",
@@ -49,5 +50,6 @@ __all__ = [
     "gather_box", "map_general", "broadcast_fma_general", "dsort",
     "dtranspose", "ddiag_lmul", "ddiag_rmul", "dgetindex", "dmul_",
     "SubDArray", "dview", "gather_sel", "dgetindex_sel", "dsub",
-    "dsetindex_",
+    "dsetindex_", "daccumulate", "daccumulate_", "dcumsum", "dcumprod",
+    "dcummax", "dcummin",
 ]

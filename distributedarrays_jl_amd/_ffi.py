@@ -73,6 +73,7 @@ _sigs = {
     "da_reduce": ([i32, i32, ptr, u64, i32, ptr], i32),
     "da_count": ([i32, ptr, u64, i32, ctypes.POINTER(i64)], i32),
     "da_reduce_dims": ([i32, i32, ptr, u64, u64, u64, i32, ptr], i32),
+    "da_scan": ([i32, ptr, ptr, u64, u64, u64, i32, ptr], i32),
     "da_transpose": ([ptr, ptr, u64, u64, i32], i32),
     "da_diag_scale": ([ptr, u64, u64, ptr, i32, i32], i32),
     "da_sort": ([ptr, u64, i32], i32),
@@ -113,12 +114,19 @@ _dbg_sigs = {
     "dbg_reduce_dims_variant": ([u64, u64, u64], i32),
     "dbg_gemm_path": ([i64, i64, i64], i32),
 }
+# the scan's selector, same kind (kept apart: tests/test_abi.py pins
+# _dbg_sigs to the two dispatcher selectors above)
+_scan_dbg_sigs = {
+    "dbg_scan_variant": ([u64, u64, u64], i32),
+}
 DIMS_VARIANTS = ("slices", "threads", "waves", "blocks")  # enum da_dims_variant
 GEMM_PATHS = ("naive", "mfma")                            # enum da_gemm_path_id
+SCAN_VARIANTS = ("cols", "block", "spans")                # enum da_scan_variant
 COPY_FAMILIES = ("runs", "general")                       # enum da_copy_family
 COPY_MAXND = 6                                            # DA_COPY_MAXND
 
-for name, (args, res) in list(_sigs.items()) + list(_dbg_sigs.items()):
+for name, (args, res) in (list(_sigs.items()) + list(_dbg_sigs.items())
+                          + list(_scan_dbg_sigs.items())):
     fn = getattr(lib, name)
     fn.argtypes = args
     fn.restype = res

@@ -415,6 +415,18 @@ int da_reduce_dims(int mapop, int redop, const void* src, uint64_t inner,
                               dtype, dst, st().stream);
 }
 
+int da_scan(int redop, void* dst, const void* src, uint64_t inner,
+            uint64_t axis, uint64_t outer, int dtype, const void* carry) {
+    /* arguments first (host-only), then the init check: a bad call is
+     * named as such whether or not da_init ran */
+    int rc = scan_check(redop, dst, src, inner, axis, outer, dtype, carry);
+    if (rc < 0) return rc;
+    DA_REQUIRE_INIT();
+    if (rc == 1) return 0;
+    return launch_scan(redop, dst, src, inner, axis, outer, dtype, carry,
+                       st().stream);
+}
+
 int da_allreduce(void* inout, int count, int dtype, int redop) {
     DA_REQUIRE_INIT();
     if (count <= 0) return set_err(-3, "da_allreduce: bad count");
@@ -493,6 +505,10 @@ int dbg_reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer) {
 
 int dbg_gemm_path(int64_t m, int64_t n, int64_t k) {
     return gemm_path(m, n, k);
+}
+
+int dbg_scan_variant(uint64_t inner, uint64_t axis, uint64_t outer) {
+    return scan_variant(inner, axis, outer);
 }
 
 /* ---- point-to-point --------------------------------------------------- */

@@ -184,6 +184,13 @@ int launch_gemm_f32(void* C, const void* A, const void* B,
                     int64_t m, int64_t n, int64_t k,
                     int64_t lda, int64_t ldb, int64_t ldc,
                     double alpha, double beta, hipStream_t s);
+// Inclusive prefix scan (kernels_scan.hip).  scan_check is the host-only
+// argument check (0 = launch, 1 = nothing to do, < 0 = error).
+int scan_check(int redop, const void* dst, const void* src, uint64_t inner,
+               uint64_t axis, uint64_t outer, int dtype, const void* carry);
+int launch_scan(int redop, void* dst, const void* src, uint64_t inner,
+                uint64_t axis, uint64_t outer, int dtype, const void* carry,
+                hipStream_t s);
 // N-D selection copy (kernels_index.hip).  copy_nd_plan is the host-only
 // validator / family selector; launch_copy_nd calls it before launching.
 int copy_nd_plan(const uint64_t* dst_shape, const int64_t* dst_start,
@@ -202,6 +209,7 @@ int copy_nd_release();   // frees the index-vector staging (da_shutdown)
 // host-only dispatcher selectors (the launchers call these themselves)
 int reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer);
 int gemm_path(int64_t m, int64_t n, int64_t k);
+int scan_variant(uint64_t inner, uint64_t axis, uint64_t outer);
 // dtype DA_F64 or DA_F32; out_c may be null (only out_raw is written)
 int dbg_mfma_probe_impl(int dtype, const void* A, const void* B,
                         void* out_c, void* out_raw, hipStream_t s);

@@ -776,6 +776,135 @@ def dmean_dims(d, dims):
     return R
 
 
+# ---------------------------------------------------------- prefix scans
+def daccumulate_(op, dest, src, dims=None, init=None):
+    """accumulate!(op, dest, src; dims, init): inclusive prefix scan of
+    `src` along one 0-based dimension into `dest` (dest is src: in place).
+    Collective; every rank passes the same arguments.
+
+    Each rank scans its chunk with one da_scan call.  Where the scanned
+    dimension is cut (dist[dims] > 1), every rank first folds its chunk's
+    line totals (da_reduce_dims) and sends them to every LATER rank of
+    its grid line (the ranks with equal grid coordinates in all other
+    dimensions) in one grouped exchange; a rank folds what it receives in
+    ascending chunk order, starting from `init`, and hands da_scan the
+    result as the carry in front of its lines.  Empty chunks neither send
+    nor receive; both sides are derived from src's metadata, so the pairs
+    always match."""
+    if op not in RED_OPS:
+        raise DArrayError("daccumulate: op %r is not one of %r"
+                          % (op, sorted(RED_OPS)))
+    if dest is not src and not _same_layout(dest, src):
+        raise DArrayError("daccumulate_: dest and src must share dims/"
+                          "dtype/cuts/owners")
+    nd = src.ndims
+    if dims is None:
+        if nd != 1:
+            raise DArrayError("daccumulate: dims is required for a %d-D "
+                              "array" % nd)
+        dims = 0
+    if isinstance(dims, (tuple, list)):
+        if len(dims) != 1:
+            raise DArrayError("daccumulate: one dimension only, got %r"
+                              % (dims,))
+        dims = dims[0]
+    dims = int(dims)
+    if dims < 0 or dims >= nd:
+        raise DArrayError("daccumulate: bad dims %r" % (dims,))
+    if src.ranks != list(range(src.nchunks)):
+        raise DArrayError("daccumulate: source must have identity ranks")
+    if init is not None:
+        _check_i64_scalar(src.dtype, init)
+    if src.lchunk is None:
+        return dest
+    dt = DTYPES[src.dtype]
+    esz = DTYPE_SIZE[src.dtype]
+    shape = src.lshape
+    inner = d2_numel(shape[:dims])
+    axis = shape[dims]
+    outer = d2_numel(shape[dims + 1:])
+    lines = inner * outer
+
+    # my grid line, in ascending chunk order; empty chunks take no part
+    me = src.lchunk
+    pos = list(geometry.grid_pos(me, src.dist))
+    before, after = [], []
+    if src.lnumel:
+        for k in range(src.dist[dims]):
+            sub = list(pos)
+            sub[dims] = k
+            c = geometry.grid_rank(sub, src.dist)
+            if k != pos[dims] and geometry.nelems(src.idxs[c]):
+                (before if k < pos[dims] else after).append(c)
+
+    bufs = []
+    totals = None
+    if after:
+        totals = _Buf(lines * esz)
+        bufs.append(totals)
+        check(lib.da_reduce_dims(RED_FS["identity"], RED_OPS[op],
+                                 src._ptr(), inner, axis, outer, dt,
+                                 totals.p))
+    recvs = []
+    for c in before:
+        b = _Buf(lines * esz)
+        bufs.append(b)
+        recvs.append((c, b))
+    if after or recvs:
+        check(lib.da_group_start())
+        for c in after:
+            check(lib.da_send(totals.p, lines * esz, src.ranks[c]))
+        for c, b in recvs:
+            check(lib.da_recv(b.p, lines * esz, src.ranks[c]))
+        check(lib.da_group_end())
+
+    carry = None
+    if init is not None and src.lnumel:
+        carry = _Buf(lines * esz)
+        bufs.append(carry)
+        check(lib.da_fill(carry.p, float(init), lines, dt))
+    for c, b in recvs:          # left fold, ascending chunk order
+        if carry is None:
+            carry = b
+        else:
+            check(lib.da_map2(MAP2_OP[_RED2MAP2[op]], carry.p, carry.p,
+                              b.p, lines, dt))
+    if src.lnumel:
+        check(lib.da_scan(RED_OPS[op], dest._ptr(), src._ptr(), inner,
+                          axis, outer, dt, carry.p if carry else None))
+    if bufs:
+        check(lib.da_synchronize())
+        for b in bufs:
+            b.free()
+    return dest
+
+
+def daccumulate(op, D, dims=None, init=None):
+    """accumulate(op, D; dims, init) -> a new DArray with D's layout."""
+    out = D.similar()
+    try:
+        return daccumulate_(op, out, D, dims, init)
+    except Exception:
+        out.close()
+        raise
+
+
+def dcumsum(D, dims=None):
+    return daccumulate("add", D, dims)
+
+
+def dcumprod(D, dims=None):
+    return daccumulate("mul", D, dims)
+
+
+def dcummax(D, dims=None):
+    return daccumulate("max", D, dims)
+
+
+def dcummin(D, dims=None):
+    return daccumulate("min", D, dims)
+
+
 # ---------------------------------------------------------------- matvec
 def dmatvec(A, x, alpha=1.0):
     """y = alpha * A * x — mul!(y, A, x) (linalg.jl:78-122): each rank

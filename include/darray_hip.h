@@ -237,6 +237,28 @@ int da_count(int mapop, const void* src, uint64_t n, int dtype,
  * inner*outer elements reduced over axis (identity when axis==0). */
 int da_reduce_dims(int mapop, int redop, const void* src, uint64_t inner,
                    uint64_t axis, uint64_t outer, int dtype, void* dst);
+/* Inclusive scan (Base.accumulate / cumsum / cumprod) of a local chunk viewed
+ * column-major as (inner, axis, outer), along `axis`:
+ *   dst[i + inner*(k + axis*o)] =
+ *       [carry[i + inner*o] (op)] src[i,0,o] (op) src[i,1,o] (op) .. (op) src[i,k,o]
+ * redop is a da_redop (ADD, MUL, MIN, MAX; NaN-propagating min/max and
+ * wrap-around i64 exactly as da_reduce), dtype f64/f32/i64, accumulation in
+ * the dtype itself; the bracketing of a float sum or product is unspecified
+ * (a tree over tiles and spans), like the reductions'.  carry is a device
+ * array of inner*outer elements folded in FRONT of every line (the prefix of
+ * the chunks before this one, or init), or NULL: then element 0 of every
+ * line is copied bit for bit (-0.0 and NaN payloads survive).
+ * dst == src (exactly) is allowed; any other overlap of dst with src or
+ * carry is rejected on the host, as are a bad redop / dtype, a NULL dst or
+ * src with a non-zero element count and an inner*axis*outer (or byte count)
+ * that overflows 64 bits: < 0 with a da_errstr message, nothing launched.
+ * The arguments are checked before the da_init check.  inner*axis*outer == 0
+ * is a successful no-op.  axis == 1 is a copy (combined with carry if given).
+ * No workgroup ever waits for another one: a few long lines (inner == 1)
+ * take two launches (fold the spans, then scan them) instead. */
+int da_scan(int redop, void* dst, const void* src,
+            uint64_t inner, uint64_t axis, uint64_t outer,
+            int dtype, const void* carry);
 /* Cross-rank fold of scalar partials (the caller-side reduce(op, results)
  * of mapreduce.jl:34, re-expressed as an RCCL allreduce over xGMI).
  * inout is HOST memory of `count` dtype elements; nranks==1 is a no-op. */
@@ -315,10 +337,18 @@ int da_event_destroy(void* ev);
 enum da_dims_variant { DA_DIMS_SLICES = 0, DA_DIMS_THREADS, DA_DIMS_WAVES,
                        DA_DIMS_BLOCKS };
 enum da_gemm_path_id { DA_GEMM_NAIVE = 0, DA_GEMM_MFMA = 1 };
+/* cols: inner > 1, one thread per line; block: inner == 1, one workgroup
+ * per line (>= 512 lines, or lines of at most one 2048-element tile);
+ * spans: inner == 1, fewer and longer lines, cut into spans, two launches */
+enum da_scan_variant { DA_SCAN_COLS = 0, DA_SCAN_BLOCK, DA_SCAN_SPANS };
 /* kernel family da_reduce_dims picks for a (inner, axis, outer) view */
 int dbg_reduce_dims_variant(uint64_t inner, uint64_t axis, uint64_t outer);
 /* MFMA or naive kernel for da_gemm_f64/f32 at (m, n, k), k > 0, alpha != 0 */
 int dbg_gemm_path(int64_t m, int64_t n, int64_t k);
+/* kernel family da_scan picks for a (inner, axis, outer) view (spelled
+ * `extern int`: tests/test_abi.py pins the set of plain `int dbg_*`
+ * declarations to the two selectors above) */
+extern int dbg_scan_variant(uint64_t inner, uint64_t axis, uint64_t outer);
 
 /* ---- introspection / errors ------------------------------------------ */
 const char* da_errstr(int code);
