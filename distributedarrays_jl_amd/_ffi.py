@@ -106,6 +106,8 @@ _sigs = {
     "da_errstr": ([i32], ctypes.c_char_p),
     "da_device_props": ([ctypes.c_char_p, i32, ctypes.POINTER(u64)], i32),
     "da_bytes_in_use": ([], u64),
+    # results taken from the pinned-slot poll / the stream-sync fallback
+    "da_dbg_reduce_waits": ([ctypes.POINTER(u64), ctypes.POINTER(u64)], i32),
 }
 
 # debug-only host-side dispatcher selectors (declared in the header's debug

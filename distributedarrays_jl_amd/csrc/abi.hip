@@ -86,8 +86,14 @@ int da_init(int device, int rank, int nranks, const char* rccl_uid_path) {
     DA_CHECK_HIP(hipMalloc(&st().red_ticket, sizeof(unsigned int)));
     DA_CHECK_HIP(hipMemset(st().red_ticket, 0, sizeof(unsigned int)));
     st().red_base = 0;
-    DA_CHECK_HIP(hipHostMalloc(&st().red_host, 16, hipHostMallocDefault));
+    // { value, sequence }: the host polls the sequence word while the
+    // kernel runs, so the slot is asked for as coherent mapped memory by
+    // name, not as whatever the default flags mean
+    DA_CHECK_HIP(hipHostMalloc(&st().red_host, 16,
+                               hipHostMallocCoherent | hipHostMallocMapped));
     memset(st().red_host, 0, 16);
+    st().red_seq = 0;
+    reduce_waits_reset();
     DA_CHECK_HIP(hipHostGetDevicePointer(&st().red_host_dev,
                                          st().red_host, 0));
     st().device = device;
@@ -509,6 +515,13 @@ int dbg_gemm_path(int64_t m, int64_t n, int64_t k) {
 
 int dbg_scan_variant(uint64_t inner, uint64_t axis, uint64_t outer) {
     return scan_variant(inner, axis, outer);
+}
+
+/* debug-only: how many flat-reduce results were taken from the poll of the
+ * pinned slot and how many from the stream-sync fallback since da_init */
+int da_dbg_reduce_waits(uint64_t* polled, uint64_t* synced) {
+    reduce_waits(polled, synced);
+    return 0;
 }
 
 /* ---- point-to-point --------------------------------------------------- */

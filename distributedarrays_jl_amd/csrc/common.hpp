@@ -40,10 +40,15 @@ struct State {
     // holds before the next launch (kernels_reduce.hip, ticket invariant)
     unsigned int* red_ticket = nullptr;
     unsigned int red_base = 0;
-    // pinned host slot (8 bytes) the flat reduce / count kernels write
-    // their result to, and the device's address of it
+    // pinned host slot the flat reduce / count kernels write their result
+    // to, 16 bytes { 8-byte value, 64-bit sequence } in coherent mapped
+    // memory, and the device's address of it.  red_seq is the sequence of
+    // the last launch that publishes into it (0 = none yet; 64 bits, so
+    // it never wraps); the slot's sequence word trails it by at most the
+    // launch in flight
     void* red_host = nullptr;
     void* red_host_dev = nullptr;
+    uint64_t red_seq = 0;
     std::mutex mem_mtx;
     std::unordered_map<void*, uint64_t> allocs;
     uint64_t bytes_in_use = 0;
@@ -97,7 +102,12 @@ constexpr int RMAXB = 8192;        // block partials (fits scratch)
 int reduce_grid(uint64_t want);    // min(want, DA_RBLOCKS cap), >= 1
 bool reduce_fused_on();            // DA_RED_FUSED != 0
 int reduce_stage2_launch(int redop, int g, int dtype, hipStream_t s);
-int reduce_result(void* out_host, size_t bytes, hipStream_t s);
+// seq: the sequence the launched kernel publishes (published_seq), or 0
+// for the two-kernel path, which publishes none and is always synced
+int reduce_result(void* out_host, size_t bytes, hipStream_t s, uint64_t seq);
+// results taken from the poll / from the stream sync since da_init
+void reduce_waits(uint64_t* polled, uint64_t* synced);
+void reduce_waits_reset();
 
 // Ticket hand-out of EVERY single-launch fan-in kernel (ticket invariant,
 // reduce_core.hpp): launch(base) starts a g-block kernel whose blocks
@@ -108,6 +118,24 @@ inline int fanin_launch(int g, L launch) {
     DA_CHECK_HIP(launch(st().red_base));
     st().red_base += (unsigned int)g;
     return 0;
+}
+
+// The same for the kernels whose result the host waits for (reduce,
+// count, expression reduce): launch(base, seq) also hands the kernel the
+// sequence it publishes next to its result, red_seq + 1, committed like
+// red_base only when the launch succeeded.
+template <typename L>
+inline int fanin_launch_seq(int g, L launch) {
+    const uint64_t seq = st().red_seq + 1;
+    int rc = fanin_launch(g, [&](unsigned int base) {
+        return launch(base, (unsigned long long)seq);
+    });
+    if (rc == 0) st().red_seq = seq;
+    return rc;
+}
+// what to wait for after a launch: its sequence, or 0 (two-kernel path)
+inline uint64_t published_seq(bool fused) {
+    return fused ? st().red_seq : 0;
 }
 
 // kernel-side entry points (implemented in kernels_*.hip)

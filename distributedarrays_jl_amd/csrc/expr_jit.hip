@@ -254,6 +254,7 @@ const char* JRARGS_DECL =
     "  void* out;\n"
     "  unsigned int base;\n"
     "  int fused;\n"
+    "  unsigned long long seq;\n"
     "};\n";
 
 // Fused mapreduce kernel for one program: evalx (gen_eval, unchanged)
@@ -330,7 +331,7 @@ std::string gen_reduce_source(const int32_t* prog, int plen, int dtype,
         "  acc = da::block_reduce_in(%d, acc, sh);\n"
         "  if (r.fused)\n"
         "    da::fanin_finish(%d, acc, (%s*)r.partials, r.ticket, r.base, "
-        "(%s*)r.out, sh);\n"
+        "(%s*)r.out, r.seq, sh);\n"
         "  else if (threadIdx.x == 0)\n"
         "    ((%s*)r.partials)[blockIdx.x] = acc;\n"
         "}\n",
@@ -487,6 +488,7 @@ struct JRArgs {
     void* out;
     unsigned int base;
     int fused;
+    unsigned long long seq;   // published next to the result when fused
 };
 
 // The caller (launch_expr_reduce) has validated the program, the layout
@@ -525,8 +527,9 @@ int launch_expr_reduce_jit(const int32_t* prog, int plen,
     r.ticket = st().red_ticket;
     r.out = st().red_host_dev;
     r.fused = fused ? 1 : 0;
-    auto launch = [&](unsigned int base) {
+    auto launch = [&](unsigned int base, unsigned long long seq) {
         r.base = base;
+        r.seq = seq;
         size_t rsz = sizeof(r);
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &r,
                        HIP_LAUNCH_PARAM_BUFFER_SIZE, &rsz,
@@ -534,8 +537,8 @@ int launch_expr_reduce_jit(const int32_t* prog, int plen,
         return hipModuleLaunchKernel(fn, (unsigned)g, 1, 1, 256, 1, 1, 0, s,
                                      nullptr, cfg);
     };
-    if (fused) return fanin_launch(g, launch);
-    DA_CHECK_HIP(launch(0u));
+    if (fused) return fanin_launch_seq(g, launch);
+    DA_CHECK_HIP(launch(0u, 0ull));
     return 0;
 }
 

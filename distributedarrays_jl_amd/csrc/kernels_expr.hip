@@ -337,7 +337,8 @@ template <typename T, typename A, bool COUNT, bool STRIDED>
 __global__ void expr_reduce_kernel(ExprProg p, ExprStrides s, uint64_t n,
                                    int redop, A* partials,
                                    unsigned int* ticket, unsigned int base,
-                                   int fused, A* out) {
+                                   int fused, A* out,
+                                   unsigned long long seq) {
     __shared__ A sh[RTPB / 64 + 1];
     auto term = [&](uint64_t i) -> T {
         if constexpr (STRIDED) return expr_strided_eval<T>(p, s, i);
@@ -358,7 +359,7 @@ __global__ void expr_reduce_kernel(ExprProg p, ExprStrides s, uint64_t n,
         acc = expr_absorb<COUNT>(redop, acc, term(j));
     acc = block_reduce_in(redop, acc, sh);
     if (fused)
-        fanin_finish(redop, acc, partials, ticket, base, out, sh);
+        fanin_finish(redop, acc, partials, ticket, base, out, seq, sh);
     else if (threadIdx.x == 0)
         partials[blockIdx.x] = acc;
 }
@@ -377,15 +378,15 @@ template <typename T, typename A, bool COUNT, bool STRIDED>
 int expr_reduce_interp(const ExprRedArgs& a) {
     A* parts = (A*)st().partials;
     A* out = (A*)st().red_host_dev;
-    auto launch = [&](unsigned int base) {
+    auto launch = [&](unsigned int base, unsigned long long seq) {
         hipLaunchKernelGGL((expr_reduce_kernel<T, A, COUNT, STRIDED>),
                            dim3(a.g), dim3(RTPB), 0, a.s, a.P, a.S, a.n,
                            a.redop, parts, st().red_ticket, base,
-                           a.fused ? 1 : 0, out);
+                           a.fused ? 1 : 0, out, seq);
         return hipGetLastError();
     };
-    if (a.fused) return fanin_launch(a.g, launch);
-    DA_CHECK_HIP(launch(0u));
+    if (a.fused) return fanin_launch_seq(a.g, launch);
+    DA_CHECK_HIP(launch(0u, 0ull));
     return 0;
 }
 
@@ -479,7 +480,8 @@ int launch_expr_reduce(const int32_t* prog, int plen, const uint64_t* dims,
         if (rc) return rc;
     }
     return reduce_result(out_host, count ? sizeof(int64_t)
-                                         : dtype_size(dtype), s);
+                                         : dtype_size(dtype), s,
+                         published_seq(fused));
 }
 
 } // namespace da

@@ -13,6 +13,7 @@
 // fold order is likewise unspecified: docs/src/index.md:208-236).
 #include "common.hpp"
 #include "reduce_core.hpp"
+#include "reduce_wait.hpp"
 #include <stdlib.h>
 
 namespace da {
@@ -73,6 +74,9 @@ __device__ __forceinline__ T block_reduce(int redop, T v) {
 // vector loads over the first n/W*W elements, then the scalar tail.
 // fold(acc, x) absorbs one source element.  Every caller is launched
 // with RTPB threads per block; the constant keeps the stride in SGPRs.
+// The vector loads are non-temporal (global_load_dwordx4 ... nt): the
+// source is read once, so keeping it in the caches only costs — 338 ->
+// 308 us per sum of 2^28 f64, same bits (profiles/r5_reduce_wait.md).
 template <int W, typename T, typename A, typename F>
 __device__ __forceinline__ A grid_accumulate(const T* __restrict__ src,
                                              uint64_t n, A acc, F fold) {
@@ -82,7 +86,7 @@ __device__ __forceinline__ A grid_accumulate(const T* __restrict__ src,
     uint64_t nv = n / W;
     const V* sv = reinterpret_cast<const V*>(src);
     for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
+        V v = __builtin_nontemporal_load(&sv[j]);
 #pragma unroll
         for (int k = 0; k < W; ++k) acc = fold(acc, (T)v[k]);
     }
@@ -122,18 +126,20 @@ __global__ void reduce_stage1_v4(int mapop, int redop,
 // ticket invariant are in reduce_core.hpp.
 //
 // `partials` is deliberately not __restrict__/const: its loads must stay
-// vector loads behind the acquire.  `out` is host-visible pinned memory.
+// vector loads behind the acquire.  `out` is the host-visible pinned slot;
+// `seq` is published next to the value (publish_result).
 template <typename T, int MOP = -1, int ROP = -1>
 __global__ void reduce_fused(int mapop, int redop, const T* __restrict__ src,
                              uint64_t n, T* partials, unsigned int* ticket,
-                             unsigned int base, T* out) {
+                             unsigned int base, T* out,
+                             unsigned long long seq) {
     if (MOP >= 0) mapop = MOP;
     if (ROP >= 0) redop = ROP;
     __shared__ T sh[RTPB / 64 + 1];
     T acc = grid_accumulate<2>(src, n, RedIdent<T>::get(redop),
         [=](T a, T x) { return red_comb(redop, a, mapf<T>(mapop, x)); });
     acc = block_reduce_in(redop, acc, sh);
-    fanin_finish(redop, acc, partials, ticket, base, out, sh);
+    fanin_finish(redop, acc, partials, ticket, base, out, seq, sh);
 }
 
 template <typename T>
@@ -168,10 +174,12 @@ template <typename T> struct FlatArgs {
 template <typename T, int MOP, int ROP>
 static int launch_flat(const FlatArgs<T>& a) {
     if (a.fused)
-        return fanin_launch(a.grid, [&](unsigned int base) {
+        return fanin_launch_seq(a.grid, [&](unsigned int base,
+                                            unsigned long long seq) {
             hipLaunchKernelGGL((reduce_fused<T, MOP, ROP>), dim3(a.grid),
                                dim3(RTPB), 0, a.s, a.mapop, a.redop, a.src,
-                               a.n, a.parts, st().red_ticket, base, a.out);
+                               a.n, a.parts, st().red_ticket, base, a.out,
+                               seq);
             return hipGetLastError();
         });
     hipLaunchKernelGGL((reduce_stage1<T, MOP, ROP>), dim3(a.grid),
@@ -217,7 +225,7 @@ static int do_reduce(int mapop, int redop, const T* src, uint64_t n,
                            redop, a.parts, g, a.out);
         DA_CHECK_HIP(hipGetLastError());
     }
-    return reduce_result(out_host, sizeof(T), s);
+    return reduce_result(out_host, sizeof(T), s, published_seq(a.fused));
 }
 
 // Exact predicate count: the 0/1 predicate of a T source is accumulated
@@ -250,12 +258,14 @@ __global__ void count_stage1(int mapop, const T* __restrict__ src,
 template <typename T>
 __global__ void count_fused(int mapop, const T* __restrict__ src, uint64_t n,
                             int64_t* partials, unsigned int* ticket,
-                            unsigned int base, int64_t* out) {
+                            unsigned int base, int64_t* out,
+                            unsigned long long seq) {
     __shared__ int64_t sh[RTPB / 64 + 1];
     int64_t acc = grid_accumulate<2>(src, n, (int64_t)0,
         [=](int64_t a, T x) { return a + predf<T>(mapop, x); });
     acc = block_reduce_in((int)DA_RED_ADD, acc, sh);
-    fanin_finish((int)DA_RED_ADD, acc, partials, ticket, base, out, sh);
+    fanin_finish((int)DA_RED_ADD, acc, partials, ticket, base, out, seq,
+                 sh);
 }
 
 template <typename T>
@@ -267,10 +277,11 @@ static int do_count(int mapop, const T* src, uint64_t n, int64_t* out_host,
     int64_t* parts = (int64_t*)st().partials;
     int64_t* out = (int64_t*)st().red_host_dev;
     if (reduce_fused_on()) {
-        rc = fanin_launch(g, [&](unsigned int base) {
+        rc = fanin_launch_seq(g, [&](unsigned int base,
+                                     unsigned long long seq) {
             hipLaunchKernelGGL(count_fused<T>, dim3(g), dim3(RTPB), 0, s,
                                mapop, src, n, parts, st().red_ticket, base,
-                               out);
+                               out, seq);
             return hipGetLastError();
         });
         if (rc) return rc;
@@ -282,7 +293,8 @@ static int do_count(int mapop, const T* src, uint64_t n, int64_t* out_host,
                            (int)DA_RED_ADD, parts, g, out);
         DA_CHECK_HIP(hipGetLastError());
     }
-    return reduce_result(out_host, sizeof(int64_t), s);
+    return reduce_result(out_host, sizeof(int64_t), s,
+                         published_seq(reduce_fused_on()));
 }
 
 int launch_count(int mapop, const void* src, uint64_t n, int dtype,
@@ -570,11 +582,52 @@ int reduce_stage2_launch(int redop, int g, int dtype, hipStream_t s) {
     return 0;
 }
 
-// The result is in the pinned host slot once the stream has drained: no
-// device-to-host copy command follows the kernels.
-int reduce_result(void* out_host, size_t bytes, hipStream_t s) {
+// DA_RED_SPIN_US: how long reduce_result polls the pinned slot before it
+// falls back to the stream sync (read once; default 2000; 0 = never poll).
+static uint64_t red_spin_us() {
+    static int64_t v = -1;
+    if (v < 0) {
+        const char* e = getenv("DA_RED_SPIN_US");
+        v = e ? atoll(e) : 2000;
+        if (v < 0) v = 2000;
+    }
+    return (uint64_t)v;
+}
+
+static uint64_t g_red_polled = 0, g_red_synced = 0;
+
+void reduce_waits(uint64_t* polled, uint64_t* synced) {
+    if (polled) *polled = g_red_polled;
+    if (synced) *synced = g_red_synced;
+}
+void reduce_waits_reset() { g_red_polled = g_red_synced = 0; }
+
+// Returns the result of the reduce just launched on `s`.  seq != 0: a
+// single-launch kernel publishes {value, seq} into the pinned slot
+// (publish_result), so the host watches the slot itself for up to
+// DA_RED_SPIN_US and, when seq arrives, returns WITHOUT a runtime call:
+// the stream is then NOT known to be drained (only this kernel's reads of
+// its source and its result store are known to be done).  Budget spent,
+// DA_RED_SPIN_US=0, or seq == 0 (the two-kernel path, which publishes no
+// sequence): the stream sync, after which the slot holds the result; a
+// kernel that faulted never publishes and its error comes back here.
+int reduce_result(void* out_host, size_t bytes, hipStream_t s,
+                  uint64_t seq) {
+    const RedSlot* slot = (const RedSlot*)st().red_host;
+    const uint64_t budget = seq ? red_spin_us() : 0;
+    if (budget && red_wait(slot, seq, budget, out_host, bytes)) {
+        ++g_red_polled;
+        return 0;
+    }
     DA_CHECK_HIP(hipStreamSynchronize(s));
-    memcpy(out_host, st().red_host, bytes);
+    if (seq && __atomic_load_n(&slot->seq, __ATOMIC_ACQUIRE) != seq)
+        return set_err(-6, "flat reduce: the stream drained but the result "
+                       "slot holds sequence %llu, not %llu",
+                       (unsigned long long)__atomic_load_n(
+                           &slot->seq, __ATOMIC_RELAXED),
+                       (unsigned long long)seq);
+    memcpy(out_host, slot->value, bytes);
+    ++g_red_synced;
     return 0;
 }
 

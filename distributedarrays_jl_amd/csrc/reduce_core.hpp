@@ -110,6 +110,31 @@ __device__ __forceinline__ void publish_partial(A* p, A v) {
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The result hand-off to the host.  `out` is the device address of the
+// 16-byte pinned host slot { 8-byte value, 64-bit sequence } (RedSlot,
+// reduce_wait.hpp).  One lane, once per launch: a system-scope store of
+// the value, then a system-scope RELEASE store of this launch's `seq`
+// into out + 8, so a host whose acquire load of the sequence word
+// returns `seq` reads this launch's value.  The release stays a release:
+// the guide's fence-free write-through form (§6 Guideline 16 R1) is
+// stated for agent-scope hand-offs inside a launch, not for host-visible
+// memory at system scope.  Two stores, never one 16-byte one: nothing
+// promises that arrives untorn.
+template <typename A>
+__device__ __forceinline__ void publish_result(A* out, A v,
+                                               unsigned long long seq) {
+    if constexpr (sizeof(A) == 8)
+        __hip_atomic_store((unsigned long long*)out,
+                           __builtin_bit_cast(unsigned long long, v),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else
+        __hip_atomic_store((unsigned int*)out,
+                           __builtin_bit_cast(unsigned int, v),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store((unsigned long long*)((char*)out + 8), seq,
+                       __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // `acc`: the block's partial (valid in thread 0).  `sh`: RTPB/64 + 1
 // shared elements — block_reduce_in's scratch plus the "I am last"
 // flag, kept in ONE __shared__ object.  Reusing sh[0..3] for the final
@@ -119,6 +144,7 @@ template <typename A>
 __device__ __forceinline__ void fanin_finish(int redop, A acc, A* partials,
                                              unsigned int* ticket,
                                              unsigned int base, A* out,
+                                             unsigned long long seq,
                                              A* sh) {
     if (threadIdx.x == 0) {
         publish_partial(partials + blockIdx.x, acc);
@@ -139,7 +165,7 @@ __device__ __forceinline__ void fanin_finish(int redop, A acc, A* partials,
     for (unsigned int j = threadIdx.x; j < gridDim.x; j += RTPB)
         facc = red_comb(redop, facc, partials[j]);
     facc = block_reduce_in(redop, facc, sh);
-    if (threadIdx.x == 0) out[0] = facc;
+    if (threadIdx.x == 0) publish_result(out, facc, seq);
 }
 
 } // namespace da

@@ -196,7 +196,9 @@ const char* da_expr_jit_errstr(void);
  * Fold-order contract: *out has EXACTLY the bits of da_expr into a dense
  * temporary followed by da_reduce(DA_REDF_IDENTITY, redop, tmp, n) /
  * da_count(DA_REDF_NONZERO, tmp, n) in the same process (DA_RV4 does not
- * apply; DA_RED_FUSED=0 and DA_EXPR_JIT=0 are honoured, same bits). */
+ * apply; DA_RED_FUSED=0 and DA_EXPR_JIT=0 are honoured, same bits).
+ * Like da_reduce, neither call drains the stream (stream contract under
+ * "reductions" below). */
 int da_expr_reduce(const int32_t* prog, int prog_len,
                    const uint64_t* dims, int nd,
                    void* const* srcs, const uint64_t* src_strides, int nsrcs,
@@ -219,17 +221,31 @@ int da_cast(void* dst, int dst_dtype, const void* src, int src_dtype,
             uint64_t n);
 
 /* ---- reductions -------------------------------------------------------*/
+/* Stream contract of the scalar results (da_reduce, da_count,
+ * da_expr_reduce, da_expr_count): the call returns once *out holds the
+ * result, and by then the reducing kernel has finished READING its
+ * sources.  It does NOT promise that the rank's stream has drained: the
+ * single-launch kernel publishes {value, sequence} into a pinned host slot
+ * and the host watches that slot for up to DA_RED_SPIN_US microseconds
+ * (default 2000) instead of synchronising the stream.  Work queued before
+ * the reduce has completed (one stream, in order); the runtime may not yet
+ * know.  A caller that needs the stream drained (to read other device
+ * results through its own channel, say) calls da_synchronize.  The stream
+ * is synchronised as before when the budget runs out (a kernel fault comes
+ * back as the HIP error then), with DA_RED_SPIN_US=0, and on the
+ * two-kernel path (DA_RED_FUSED=0, DA_RV4=1). */
 /* Local (per-chunk) mapreduce stage: LDS + wavefront-shuffle tree.
  * Result written to *out as the dtype's own scalar type (f64/f32/i64) —
  * the per-worker mapreduce(f, op, localpart(d)) of mapreduce.jl:31.
- * n == 0 returns the fold identity. */
+ * n == 0 returns the fold identity.  Does not drain the stream (above). */
 int da_reduce(int mapop, int redop, const void* src, uint64_t n, int dtype,
               void* out);
 /* Exact predicate count (count(f, A), mapreduce.jl:115-122): mapop must be
  * a predicate (DA_REDF_ISNAN / ISFINITE / NONZERO).  The 0/1 values are
  * accumulated in a 64-bit integer on the device whatever the source dtype,
  * so *out is exact for every n (a float accumulator rounds above 2^24).
- * Fold across ranks with da_allreduce(out, 1, DA_I64, DA_RED_ADD). */
+ * Fold across ranks with da_allreduce(out, 1, DA_I64, DA_RED_ADD).
+ * Does not drain the stream (stream contract above). */
 int da_count(int mapop, const void* src, uint64_t n, int dtype,
              int64_t* out);
 /* Per-chunk dims-reduction (src/mapreduce.jl:42-94, mapreducedim_within):
@@ -349,6 +365,10 @@ int dbg_gemm_path(int64_t m, int64_t n, int64_t k);
  * `extern int`: tests/test_abi.py pins the set of plain `int dbg_*`
  * declarations to the two selectors above) */
 extern int dbg_scan_variant(uint64_t inner, uint64_t axis, uint64_t outer);
+/* how many scalar results (da_reduce, da_count, da_expr_reduce,
+ * da_expr_count) were taken from the poll of the pinned slot and how many
+ * from the stream-sync fallback since da_init; either pointer may be NULL */
+int da_dbg_reduce_waits(uint64_t* polled, uint64_t* synced);
 
 /* ---- introspection / errors ------------------------------------------ */
 const char* da_errstr(int code);
