@@ -32,7 +32,7 @@ from .ops import (map_, dmap, map2_, elementwise, map2_scalar_, elementwise_scal
                   broadcast_fma_general, dsort, dtranspose, ddiag_lmul, ddiag_rmul,
                   dgetindex, dmul_, gather_sel, dgetindex_sel, dsub,
                   dsetindex_, daccumulate, daccumulate_, dcumsum, dcumprod,
-                  dcummax, dcummin)
+                  dcummax, dcummin, dfilter, dfindall, dsetmask_)
 
 __all__ = [
     "DArray", "DArrayError", "comm", "geometry", "plan", "spmd", "expr",
@@ -51,5 +51,5 @@ __all__ = [
     "dtranspose", "ddiag_lmul", "ddiag_rmul", "dgetindex", "dmul_",
     "SubDArray", "dview", "gather_sel", "dgetindex_sel", "dsub",
     "dsetindex_", "daccumulate", "daccumulate_", "dcumsum", "dcumprod",
-    "dcummax", "dcummin",
+    "dcummax", "dcummin", "dfilter", "dfindall", "dsetmask_",
 ]

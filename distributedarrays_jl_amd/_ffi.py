@@ -74,6 +74,8 @@ _sigs = {
     "da_count": ([i32, ptr, u64, i32, ctypes.POINTER(i64)], i32),
     "da_reduce_dims": ([i32, i32, ptr, u64, u64, u64, i32, ptr], i32),
     "da_scan": ([i32, ptr, ptr, u64, u64, u64, i32, ptr], i32),
+    "da_compact": ([ptr, u64, ptr, i32, ptr, i32, u64, i64], i32),
+    "da_expand": ([ptr, i32, ptr, i32, u64, ptr, u64, i32], i32),
     "da_transpose": ([ptr, ptr, u64, u64, i32], i32),
     "da_diag_scale": ([ptr, u64, u64, ptr, i32, i32], i32),
     "da_sort": ([ptr, u64, i32], i32),
@@ -126,6 +128,7 @@ GEMM_PATHS = ("naive", "mfma")                            # enum da_gemm_path_id
 SCAN_VARIANTS = ("cols", "block", "spans")                # enum da_scan_variant
 COPY_FAMILIES = ("runs", "general")                       # enum da_copy_family
 COPY_MAXND = 6                                            # DA_COPY_MAXND
+COMPACT_TILE = 2048                                       # DA_COMPACT_TILE
 
 for name, (args, res) in (list(_sigs.items()) + list(_dbg_sigs.items())
                           + list(_scan_dbg_sigs.items())):

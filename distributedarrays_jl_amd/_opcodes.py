@@ -28,6 +28,10 @@ MAP2_OPS = [
 ]
 MAP2_OP = {name: i for i, name in enumerate(MAP2_OPS)}
 
+# enum da_cmpop: comparisons, valid only in the binary slot of an expr
+# program (value 1 or 0 in the program's dtype); every dtype takes them
+CMP_OPS = {"eq": 64, "ne": 65, "lt": 66, "le": 67, "gt": 68, "ge": 69}
+
 RED_OPS = {"add": 0, "mul": 1, "min": 2, "max": 3}
 RED_FS = {"identity": 0, "abs": 1, "abs2": 2, "isnan": 3, "isfinite": 4,
           "nonzero": 5}

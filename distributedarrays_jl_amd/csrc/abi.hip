@@ -433,6 +433,30 @@ int da_scan(int redop, void* dst, const void* src, uint64_t inner,
                        st().stream);
 }
 
+int da_compact(void* dst, uint64_t dst_cap, const void* src, int dtype,
+               const void* mask, int mask_dtype, uint64_t n,
+               int64_t index_base) {
+    /* arguments first (host-only), then the init check, as da_scan */
+    int rc = compact_check(dst, dst_cap, src, dtype, mask, mask_dtype, n);
+    if (rc < 0) return rc;
+    DA_REQUIRE_INIT();
+    if (rc == 1) return 0;
+    return launch_compact(dst, dst_cap, src, dtype, mask, mask_dtype, n,
+                          index_base, st().stream);
+}
+
+int da_expand(void* dst, int dtype, const void* mask, int mask_dtype,
+              uint64_t n, const void* src, uint64_t src_n,
+              int src_broadcast) {
+    int rc = expand_check(dst, dtype, mask, mask_dtype, n, src, src_n,
+                          src_broadcast);
+    if (rc < 0) return rc;
+    DA_REQUIRE_INIT();
+    if (rc == 1) return 0;
+    return launch_expand(dst, dtype, mask, mask_dtype, n, src, src_n,
+                         src_broadcast, st().stream);
+}
+
 int da_allreduce(void* inout, int count, int dtype, int redop) {
     DA_REQUIRE_INIT();
     if (count <= 0) return set_err(-3, "da_allreduce: bad count");

@@ -219,6 +219,20 @@ int scan_check(int redop, const void* dst, const void* src, uint64_t inner,
 int launch_scan(int redop, void* dst, const void* src, uint64_t inner,
                 uint64_t axis, uint64_t outer, int dtype, const void* carry,
                 hipStream_t s);
+// Stream compaction and its inverse (kernels_compact.hip).  The *_check
+// functions are the host-only argument checks (0 = launch, 1 = nothing to
+// do, < 0 = error).
+int compact_check(const void* dst, uint64_t dst_cap, const void* src,
+                  int dtype, const void* mask, int mask_dtype, uint64_t n);
+int launch_compact(void* dst, uint64_t dst_cap, const void* src, int dtype,
+                   const void* mask, int mask_dtype, uint64_t n,
+                   int64_t index_base, hipStream_t s);
+int expand_check(const void* dst, int dtype, const void* mask,
+                 int mask_dtype, uint64_t n, const void* src,
+                 uint64_t src_n, int src_broadcast);
+int launch_expand(void* dst, int dtype, const void* mask, int mask_dtype,
+                  uint64_t n, const void* src, uint64_t src_n,
+                  int src_broadcast, hipStream_t s);
 // N-D selection copy (kernels_index.hip).  copy_nd_plan is the host-only
 // validator / family selector; launch_copy_nd calls it before launching.
 int copy_nd_plan(const uint64_t* dst_shape, const int64_t* dst_start,

@@ -207,7 +207,8 @@ int validate_expr(const char* who, const int32_t* prog, int plen, int nsrcs,
                 return set_err(-3, "%s: bad unary at %d", who, pc);
             break;
         case 3:
-            if (sp < 2 || idx >= DA_OP2__N)
+            if (sp < 2 || !(idx < DA_OP2__N ||
+                            (idx >= DA_CMP_EQ && idx < DA_CMP__END)))
                 return set_err(-3, "%s: bad binary at %d", who, pc);
             --sp; break;
         default:

@@ -132,6 +132,14 @@ __device__ __forceinline__ T apply_map2(int op, T a, T b) {
     }
     case DA_OP2_POW: return pow(a, b);
     case DA_OP2_ATAN2: return atan2(a, b);
+    // comparisons (da_cmpop): 1 or 0; IEEE, so a NaN operand gives 0
+    // everywhere but NE
+    case DA_CMP_EQ: return a == b ? (T)1 : (T)0;
+    case DA_CMP_NE: return a != b ? (T)1 : (T)0;
+    case DA_CMP_LT: return a < b ? (T)1 : (T)0;
+    case DA_CMP_LE: return a <= b ? (T)1 : (T)0;
+    case DA_CMP_GT: return a > b ? (T)1 : (T)0;
+    case DA_CMP_GE: return a >= b ? (T)1 : (T)0;
     }
     return a;
 }
@@ -153,6 +161,13 @@ __device__ __forceinline__ int64_t apply_map2_i64(int op, int64_t a, int64_t b) 
     case DA_OP2_XOR: return a ^ b;
     case DA_OP2_MIN2: return a < b ? a : b;
     case DA_OP2_MAX2: return a > b ? a : b;
+    // comparisons (da_cmpop): signed and exact, no subtraction to wrap
+    case DA_CMP_EQ: return a == b ? 1 : 0;
+    case DA_CMP_NE: return a != b ? 1 : 0;
+    case DA_CMP_LT: return a < b ? 1 : 0;
+    case DA_CMP_LE: return a <= b ? 1 : 0;
+    case DA_CMP_GT: return a > b ? 1 : 0;
+    case DA_CMP_GE: return a >= b ? 1 : 0;
     }
     return a;
 }

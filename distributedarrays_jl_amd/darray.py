@@ -358,9 +358,19 @@ class DArray:
         Collective at nranks>1: every rank must index identically.
         Scalars gate on allowscalar; ranges gather via the makelocal
         box path, stepped slices and lists via the selection gather;
-        both return a numpy array on every rank."""
+        both return a numpy array on every rank.
+        D[M] with M a single DArray or expr.Expr of D's dims is mask
+        indexing (Julia's D[mask]): the elements where M is nonzero, in
+        global column-major order (ops.dfilter, collected)."""
         if not isinstance(key, tuple):
             key = (key,)
+        if _is_mask_key(key):
+            from . import ops
+            kept = ops.dfilter(key[0], self)
+            try:
+                return kept.collect()
+            finally:
+                kept.close()
         if len(key) != self.ndims:
             raise _ffi.DArrayError(
                 "indexing needs %d subscripts" % self.ndims)
@@ -399,9 +409,16 @@ class DArray:
         With ranges, stepped slices or integer lists among the subscripts
         (outer product, as in Julia) v is a scalar, a numpy array, a
         DArray or a SubDArray of the selection's shape; a repeated entry
-        in an index list raises DArrayError."""
+        in an index list raises DArrayError.
+        D[M] = v with M a single DArray or expr.Expr is mask assignment
+        (ops.dsetmask_): v a scalar, or a 1-D numpy array / DVector with
+        one value per true element."""
         if not isinstance(key, tuple):
             key = (key,)
+        if _is_mask_key(key):
+            from . import ops
+            ops.dsetmask_(self, key[0], value)
+            return
         if not all(isinstance(k, (int, np.integer)) for k in key):
             from . import ops, plan
             sel, squeeze = plan.sel_normalize(key, self.dims)
@@ -463,6 +480,16 @@ class DArray:
         return ("DArray(dims=%r, dist=%r, dtype=%s, rank=%d/%d, lshape=%r)"
                 % (self.dims, self.dist, self.dtype, self.rank, self.nranks,
                    self.lshape))
+
+
+def _is_mask_key(key):
+    """True for a subscript tuple that is one DArray or expr.Expr: a mask
+    over the whole array.  (Per-dimension boolean vectors and numpy bool
+    arrays are not masks here; plan.sel_normalize rejects them.)"""
+    if len(key) != 1:
+        return False
+    from .expr import Expr
+    return isinstance(key[0], (DArray, Expr))
 
 
 def _has_strided(key):

@@ -15,6 +15,8 @@ Usage (mirrors `D .= A .- M .* sin.(C)`):
     G = E.materialize(e)        # allocating (Base.materialize / copy)
     s = E.reduce("add", e)      # mapreduce over the tree, nothing stored
     k = E.count(e)              # exact number of nonzero values
+    k = E.count(E.ref(A) > 0.5) # comparisons: <, <=, >, >=, E.eq, E.ne
+                                # (1 / 0 in the tree's dtype)
 
 Numerics: da_expr shares the scalar functor tables with da_map/da_map2
 (csrc/mapops.hpp), so a fused chain is bit-identical to the equivalent
@@ -22,7 +24,7 @@ sequence of single-op kernels."""
 import ctypes
 
 from ._ffi import check, lib, DArrayError
-from ._opcodes import (DTYPES, MAP_OP, MAP2_OP, RED_OPS,
+from ._opcodes import (DTYPES, MAP_OP, MAP2_OP, CMP_OPS, RED_OPS,
                        I64_MAP_OPS, I64_MAP2_OPS)
 
 K_UNARY, K_ARG, K_CONST, K_BINARY = 0, 1, 2, 3
@@ -66,6 +68,20 @@ class Expr:
     def __mod__(self, o):
         return Binary("mod", self, wrap(o))
 
+    # comparisons: 1 / 0 in the tree's dtype.  == and != stay Python's
+    # identity comparison (an Expr is hashable); spell them eq() / ne().
+    def __lt__(self, o):
+        return Binary("lt", self, wrap(o))
+
+    def __le__(self, o):
+        return Binary("le", self, wrap(o))
+
+    def __gt__(self, o):
+        return Binary("gt", self, wrap(o))
+
+    def __ge__(self, o):
+        return Binary("ge", self, wrap(o))
+
     def __neg__(self):
         return Unary("neg", self)
 
@@ -96,7 +112,7 @@ class Unary(Expr):
 
 class Binary(Expr):
     def __init__(self, op, a, b):
-        if op not in MAP2_OP:
+        if op not in MAP2_OP and op not in CMP_OPS:
             raise DArrayError("expr: unknown binary op %r" % op)
         self.op, self.a, self.b = op, a, b
 
@@ -142,7 +158,7 @@ def _make_binary(name):
 
 
 for _name in ("min2", "max2", "atan2", "idiv", "rem", "and_", "or_",
-              "xor"):
+              "xor") + tuple(CMP_OPS):
     globals()[_name] = _make_binary(_name.rstrip("_"))
 
 
@@ -180,7 +196,9 @@ def compile_expr(e):
         elif isinstance(node, Binary):
             walk(node.a)
             walk(node.b)
-            prog.append((K_BINARY << 8) | MAP2_OP[node.op])
+            prog.append((K_BINARY << 8) | (CMP_OPS[node.op]
+                                           if node.op in CMP_OPS
+                                           else MAP2_OP[node.op]))
         else:
             raise DArrayError("expr: bad node %r" % type(node))
 
@@ -221,7 +239,7 @@ def _validate(dest, prog, args, consts):
                 name = [k for k, v in MAP_OP.items() if v == idx][0]
                 if name not in I64_MAP_OPS:
                     raise DArrayError("expr: op %r invalid for i64" % name)
-            if kind == K_BINARY:
+            if kind == K_BINARY and idx not in CMP_OPS.values():
                 name = [k for k, v in MAP2_OP.items() if v == idx][0]
                 if name not in I64_MAP2_OPS:
                     raise DArrayError("expr: op %r invalid for i64" % name)
@@ -424,6 +442,8 @@ def reduce(op, e):
 
 def count(e):
     """count(!iszero, bc): the exact number of nonzero elements of the
-    tree's values (a NaN counts), as an int.  Predicates are composed
-    from the op tables, e.g. x > c as sign(max2(x - c, 0)).  Collective."""
+    tree's values (a NaN counts), as an int.  Predicates are comparison
+    trees, e.g. E.count(E.ref(x) > c) or E.count(E.eq(a, b)): IEEE for
+    floats (a comparison with NaN is false, except ne), exact signed
+    comparison for i64.  Collective."""
     return int(_fused(wrap(e), None))

@@ -1871,3 +1871,237 @@ def ddiag_lmul(dvec, D):
 def ddiag_rmul(D, dvec):
     """rmul!(DA, Diagonal(d)) — linalg.jl:179-187 (column scaling)."""
     return _diag_scale(D, dvec, 1)
+
+
+# ------------------------------------------- masks: filter / findall / set
+class _Temps:
+    """Device temporaries of one mask operation, freed together."""
+
+    def __init__(self):
+        self.arrays, self.bufs = [], []
+
+    def array(self, d):
+        self.arrays.append(d)
+        return d
+
+    def buf(self, b):
+        if b is not None:
+            self.bufs.append(b)
+        return b
+
+    def free(self):
+        if self.arrays or self.bufs:
+            check(lib.da_synchronize())
+        for d in self.arrays:
+            d.close()
+        for b in self.bufs:
+            b.free()
+        self.arrays, self.bufs = [], []
+
+
+def _resolve_mask(m, D, tmp):
+    """The mask as a DArray of D's dims (D None: the mask's own dims).  m
+    is a DArray (nonzero = true, any dtype), an expr.Expr (materialised
+    into a temporary) or a callable given expr.ref(D).  A dims mismatch
+    raises before anything is allocated or moved."""
+    from . import expr as E
+    if isinstance(m, DArray):
+        M = m
+        dims = M.dims
+    else:
+        if not isinstance(m, E.Expr) and callable(m):
+            if D is None:
+                raise DArrayError("a predicate needs the array it tests")
+            m = _tree(m, (D,))
+        if not isinstance(m, E.Expr):
+            raise DArrayError("a mask is a DArray, an expr.Expr or a "
+                              "predicate, got %r" % type(m))
+        M = None
+        dims = E._domain(E.compile_expr(m)[1])[0]
+    if D is not None and tuple(dims) != tuple(D.dims):
+        raise DArrayError("mask dims %r do not match the array's %r"
+                          % (tuple(dims), tuple(D.dims)))
+    if M is None:
+        M = tmp.array(E.materialize(m))
+    return M
+
+
+def _linear_order(D):
+    """True when the chunks, taken in rank order, hold the array in global
+    column-major order: the grid cuts the last dimension alone and chunk c
+    lives on rank c.  Always true for a DVector with identity owners and at
+    one rank."""
+    return (all(c == 1 for c in D.dist[:-1])
+            and list(D.ranks) == list(range(D.nchunks)))
+
+
+def _last_dim_dist(D):
+    return (1,) * (D.ndims - 1) + (D.nranks,)
+
+
+def _local_mask(M, D, tmp):
+    """(pointer, dtype) of the mask over D's local box: M's own chunk when
+    its boxes and owners are D's, else gathered onto them (makelocal)."""
+    if list(M.idxs) == list(D.idxs) and M.ranks == D.ranks:
+        return M._ptr(), M.dtype
+    buf, _ = gather_box(M, _dest_boxes(D))
+    tmp.buf(buf)
+    return (buf.p if buf is not None else None), M.dtype
+
+
+def _shared_counts(D, mptr, mdtype):
+    """Every rank's number of true mask elements, as a list: one da_count
+    per rank, then ONE allreduce (ADD) of an nranks-long i64 vector in
+    which each rank filled its own slot."""
+    k = ctypes.c_int64(0)
+    if D.lnumel:
+        check(lib.da_count(RED_FS["nonzero"], mptr, D.lnumel,
+                           DTYPES[mdtype], ctypes.byref(k)))
+    counts = (ctypes.c_int64 * D.nranks)()
+    counts[D.rank] = k.value
+    if D.nranks > 1:
+        check(lib.da_allreduce(counts, D.nranks, DTYPES["i64"],
+                               RED_OPS["add"]))
+    return [int(c) for c in counts]
+
+
+def _compact(mask, D, want_index):
+    tmp = _Temps()
+    try:
+        M = _resolve_mask(mask, D, tmp)
+        if D is None:
+            D = M
+        if not _linear_order(D):
+            dist = _last_dim_dist(D)
+            if not want_index:
+                D = tmp.array(redistribute(D, dist))
+                M = tmp.array(redistribute(M, dist))
+            else:
+                D = M = tmp.array(redistribute(M, dist))
+        mptr, mdtype = _local_mask(M, D, tmp)
+        counts = _shared_counts(D, mptr, mdtype)
+        dtype = "i64" if want_index else D.dtype
+        R = DArray.from_chunk_sizes(counts, dtype)
+        k = counts[D.rank]
+        try:
+            if D.lnumel and k:
+                # first global linear index of this chunk (findall)
+                base = d2_numel(D.dims[:-1]) * D.lidx[-1][0]
+                check(lib.da_compact(R._ptr(), k,
+                                     None if want_index else D._ptr(),
+                                     DTYPES[dtype], mptr, DTYPES[mdtype],
+                                     D.lnumel, base))
+        except Exception:
+            R.close()
+            raise
+        return R
+    finally:
+        tmp.free()
+
+
+def dfilter(pred_or_mask, D):
+    """filter(f, D) / D[mask]: a new (ragged) DVector of D's dtype holding
+    the elements of D where the mask is true, in GLOBAL column-major
+    order.  The mask is a DArray of D's dims (nonzero = true, NaN too; any
+    dtype and any layout: it is localised onto D's boxes), an expr.Expr
+    such as E.ref(D) > 0.5, or a predicate called with E.ref(D).
+    Collective.
+
+    All on the device: an exact count per rank (da_count), one allreduce
+    of the nranks counts, then a stable stream compaction of each chunk
+    (da_compact).  Rank r's chunk of the result is rank r's survivors, so
+    no element crosses ranks — which is global order only when the grid
+    cuts the last dimension alone (any DVector; dist (1, .., 1, P)).  For
+    any other grid D and the mask are first redistributed to
+    (1, .., 1, nranks); the copies are freed afterwards."""
+    return _compact(pred_or_mask, D, False)
+
+
+def dfindall(pred_or_mask, D=None):
+    """findall(f, D) / findall(mask): a ragged i64 DVector of the 0-based
+    global column-major linear indices of the true elements, ascending.
+    Masks and layouts as dfilter (a predicate needs D); collective."""
+    return _compact(pred_or_mask, D, True)
+
+
+def dsetmask_(D, mask, v):
+    """D[mask] = v / D[mask] .= c, in place; collective.  The mask is as in
+    dfilter.  v is a Python scalar (every true position gets it; an i64
+    value must be exact in a double, |v| <= 2^53), or a 1-D numpy array or
+    a DVector (any cuts) of D's dtype whose length is the global number of
+    true elements K: the j-th true element in global column-major order
+    gets v[j].  A wrong length raises DArrayError on every rank before D
+    is written.
+
+    A scalar assignment is order-free and runs on D's own chunks.  For a
+    vector v on a grid that cuts another dimension than the last, D and
+    the mask are redistributed to (1, .., 1, nranks), expanded there
+    (da_expand) and the result is copied back onto D's boxes."""
+    import numbers
+    tmp = _Temps()
+    try:
+        scalar = isinstance(v, numbers.Real)
+        if scalar:
+            _check_i64_scalar(D.dtype, v)
+        elif isinstance(v, DArray):
+            if v.ndims != 1 or v.dtype != D.dtype:
+                raise DArrayError("dsetmask_: values must be a DVector of "
+                                  "dtype %s" % D.dtype)
+        elif isinstance(v, np.ndarray):
+            if v.ndim != 1:
+                raise DArrayError("dsetmask_: values must be 1-D")
+        else:
+            raise DArrayError("dsetmask_: values are a scalar, a 1-D "
+                              "numpy array or a DVector, got %r" % type(v))
+        M = _resolve_mask(mask, D, tmp)
+        npdt = np.dtype(NUMPY_DTYPES[D.dtype])
+        esz = DTYPE_SIZE[D.dtype]
+        if scalar:
+            mptr, mdtype = _local_mask(M, D, tmp)
+            if D.lnumel:
+                one = np.array([v]).astype(npdt)
+                src = tmp.buf(_Buf(esz))
+                check(lib.da_h2d(src.p, one.ctypes.data_as(ctypes.c_void_p),
+                                 esz))
+                check(lib.da_expand(D._ptr(), DTYPES[D.dtype], mptr,
+                                    DTYPES[mdtype], D.lnumel, src.p, 1, 1))
+            return D
+        W = D
+        if not _linear_order(D):
+            dist = _last_dim_dist(D)
+            W = tmp.array(redistribute(D, dist))
+            M = tmp.array(redistribute(M, dist))
+        mptr, mdtype = _local_mask(M, W, tmp)
+        counts = _shared_counts(W, mptr, mdtype)
+        K = sum(counts)
+        vsize = v.size
+        if vsize != K:
+            raise DArrayError("dsetmask_: %d values for %d true mask "
+                              "elements" % (vsize, K))
+        k = counts[W.rank]
+        off = sum(counts[:W.rank])
+        if isinstance(v, DArray):
+            boxes = [None] * W.nranks
+            o = 0
+            for r in range(W.nranks):
+                if counts[r]:
+                    boxes[r] = ((o, o + counts[r]),)
+                o += counts[r]
+            src, _ = gather_box(v, boxes)
+            tmp.buf(src)
+        elif k:
+            part = np.ascontiguousarray(v[off:off + k], dtype=npdt)
+            src = tmp.buf(_Buf(k * esz))
+            check(lib.da_h2d(src.p, part.ctypes.data_as(ctypes.c_void_p),
+                             k * esz))
+        if W.lnumel and k:
+            check(lib.da_expand(W._ptr(), DTYPES[W.dtype], mptr,
+                                DTYPES[mdtype], W.lnumel, src.p, k, 0))
+        if W is not D:
+            back, _ = gather_box(W, _dest_boxes(D))
+            tmp.buf(back)
+            if back is not None and D.lnumel:
+                check(lib.da_d2d(D._ptr(), back.p, D.lnumel * esz))
+        return D
+    finally:
+        tmp.free()

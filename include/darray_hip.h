@@ -61,6 +61,15 @@ enum da_map2op {
     DA_OP2__N
 };
 
+/* comparisons, usable in the binary slot (kind 3) of an expr program;
+ * value 1 or 0 in the program's dtype (the Bool-array analog, like
+ * DA_OP_ISNAN).  IEEE for floats: every comparison with a NaN is 0
+ * except NE, which is 1; -0.0 == 0.0.  i64: signed, exact.  Not accepted
+ * by da_map2 / da_map2_scalar (the Broadcasted comparisons of
+ * src/broadcast.jl:65-98, the predicates of src/mapreduce.jl:97-131). */
+enum da_cmpop { DA_CMP_EQ = 64, DA_CMP_NE, DA_CMP_LT, DA_CMP_LE,
+                DA_CMP_GT, DA_CMP_GE, DA_CMP__END };
+
 /* reduction: redop x mapop (src/mapreduce.jl:17-39, :97-131) */
 enum da_redop  { DA_RED_ADD = 0, DA_RED_MUL, DA_RED_MIN, DA_RED_MAX };
 enum da_redf   { DA_REDF_IDENTITY = 0, DA_REDF_ABS, DA_REDF_ABS2,
@@ -163,8 +172,8 @@ int da_bcast_fma(void* d, const void* a, const void* b, double c,
  *
  * prog: postfix int32 program, kind = ins>>8, idx = ins&0xff:
  *   kind 0 = unary da_mapop on stack top; kind 1 = push argument idx;
- *   kind 2 = push constant idx; kind 3 = binary da_map2op (pops rhs
- *   then lhs).  Stack depth <= DA_EXPR_MAXSTACK (validated).
+ *   kind 2 = push constant idx; kind 3 = binary da_map2op or da_cmpop
+ *   (pops rhs then lhs).  Stack depth <= DA_EXPR_MAXSTACK (validated).
  * dst_dims/nd: destination LOCAL chunk shape (column-major), nd <= 4.
  * src_strides: nsrcs x nd element strides (row-major per arg); a 0
  *   stride expands a Julia-broadcast singleton dim.  NULL = every arg
@@ -275,6 +284,41 @@ int da_reduce_dims(int mapop, int redop, const void* src, uint64_t inner,
 int da_scan(int redop, void* dst, const void* src,
             uint64_t inner, uint64_t axis, uint64_t outer,
             int dtype, const void* carry);
+/* Stream compaction (filter(f, A) / findall / A[mask]) and its inverse
+ * (A[mask] = v) of a local chunk of n elements.
+ * Mask truth everywhere below: element != 0 in the mask's own dtype, so a
+ * NaN is true and -0.0 is false — the DA_REDF_NONZERO rule of da_count,
+ * whose result is the number kept.  dtype and mask_dtype are each f64, f32
+ * or i64, independently; data moves as raw 4- / 8-byte words (bit-exact),
+ * element alignment only; n, every index and every position are 64-bit.
+ * Three stream-ordered steps on the rank's stream (count the true elements
+ * of every DA_COMPACT_TILE-element tile, scan the counts with da_scan's
+ * kernels, scatter); no workgroup ever waits for another one and no atomic
+ * hands out positions, so the order is stable and the result
+ * deterministic.  Neither call synchronises: the caller sizes dst from
+ * da_count(DA_REDF_NONZERO, mask, ..).
+ * Checked on the host before the da_init check, < 0 with a da_errstr
+ * message and nothing launched: a bad dtype / mask_dtype, a NULL pointer
+ * with a non-zero count, a forbidden overlap, a byte count that overflows
+ * 64 bits.  n == 0 is a successful no-op; dst_cap == 0 / src_n == 0 is
+ * legal and stores nothing. */
+#define DA_COMPACT_TILE 2048
+/* dst[j] = src[i] for the j-th (0-based) i in increasing order with
+ * mask[i] != 0; with src == NULL, dst is int64_t and gets index_base + i
+ * (findall).  Only j < dst_cap is stored: a too-small dst_cap drops the
+ * tail and never writes outside dst.  Stable.  src == mask is fine (both
+ * are only read); dst overlapping src or mask is rejected. */
+int da_compact(void* dst, uint64_t dst_cap, const void* src, int dtype,
+               const void* mask, int mask_dtype, uint64_t n,
+               int64_t index_base);
+/* The inverse: for the j-th true i, dst[i] = src_broadcast ? src[0] : src[j]
+ * (only j < src_n is stored; a broadcast source with src_n > 0 reaches
+ * every true i); every other dst[i] is left untouched.  dst == mask
+ * (exactly, with equal element sizes) is allowed: each thread loads
+ * mask[i] before it stores dst[i].  Any other overlap of dst with mask or
+ * src is rejected. */
+int da_expand(void* dst, int dtype, const void* mask, int mask_dtype,
+              uint64_t n, const void* src, uint64_t src_n, int src_broadcast);
 /* Cross-rank fold of scalar partials (the caller-side reduce(op, results)
  * of mapreduce.jl:34, re-expressed as an RCCL allreduce over xGMI).
  * inout is HOST memory of `count` dtype elements; nranks==1 is a no-op. */
