@@ -25,7 +25,8 @@ from .ops import (map_, dmap, map2_, elementwise, map2_scalar_, elementwise_scal
                   add_, scale_, mapreduce, dsum, dprod, dmaximum, dminimum,
                   dextrema, dmean, dvar, dstd, dcount, dall, dany, ddot, dnorm, dmatmul, dreduce_dims,
                   dsum_dims, dprod_dims, dmaximum_dims, dminimum_dims,
-                  dmean_dims, dmatvec, dmatvec_adj, gather_box, map_general,
+                  dmean_dims, dvar_dims, dstd_dims, dcount_dims, dall_dims,
+                  dany_dims, dmatvec, dmatvec_adj, gather_box, map_general,
                   map_localparts, map_localparts_, redistribute,
                   dmapslices, dppeval, dcast, dreshape,
                   map2_general,
@@ -43,7 +44,8 @@ __all__ = [
     "add_", "scale_", "mapreduce", "dsum", "dprod", "dmaximum",
     "dminimum", "dextrema", "dmean", "dvar", "dstd", "dcount", "dall", "dany", "ddot", "dnorm", "dmatmul",
     "dreduce_dims", "dsum_dims", "dprod_dims", "dmaximum_dims",
-    "dminimum_dims", "dmean_dims", "dmatvec", "dmatvec_adj",
+    "dminimum_dims", "dmean_dims", "dvar_dims", "dstd_dims", "dcount_dims",
+    "dall_dims", "dany_dims", "dmatvec", "dmatvec_adj",
     "map_localparts", "map_localparts_", "redistribute",
     "dmapslices", "dppeval", "dcast", "dreshape",
     "map2_general",

@@ -63,6 +63,8 @@ _sigs = {
                         i32, i32, ptr], i32),
     "da_expr_count": ([ptr, i32, ptr, i32, ptr, ptr, i32, ptr, i32, u64,
                        i32, ctypes.POINTER(i64)], i32),
+    "da_expr_reduce_dims": ([ptr, i32, ptr, i32, ptr, ptr, i32, ptr, i32,
+                             i32, ctypes.c_uint32, i32, ptr], i32),
     "da_expr_jit_state": ([], i32),
     "da_expr_jit_errstr": ([], ctypes.c_char_p),
     "da_map2_scalar": ([i32, ptr, ptr, f64, i32, u64, i32], i32),
@@ -123,15 +125,24 @@ _dbg_sigs = {
 _scan_dbg_sigs = {
     "dbg_scan_variant": ([u64, u64, u64], i32),
 }
+# the fused dims-reduction's selector, kept apart for the same reason
+_expr_dims_dbg_sigs = {
+    "dbg_expr_dims_variant": ([ptr, i32, ctypes.c_uint32,
+                               ctypes.POINTER(ctypes.c_uint32),
+                               ctypes.POINTER(ctypes.c_uint32)], i32),
+}
 DIMS_VARIANTS = ("slices", "threads", "waves", "blocks")  # enum da_dims_variant
 GEMM_PATHS = ("naive", "mfma")                            # enum da_gemm_path_id
 SCAN_VARIANTS = ("cols", "block", "spans")                # enum da_scan_variant
+EXPR_DIMS_VARIANTS = ("lanes", "wave", "block")     # enum da_expr_dims_variant
+EXPR_COUNT = -1                                           # DA_EXPR_COUNT
 COPY_FAMILIES = ("runs", "general")                       # enum da_copy_family
 COPY_MAXND = 6                                            # DA_COPY_MAXND
 COMPACT_TILE = 2048                                       # DA_COMPACT_TILE
 
 for name, (args, res) in (list(_sigs.items()) + list(_dbg_sigs.items())
-                          + list(_scan_dbg_sigs.items())):
+                          + list(_scan_dbg_sigs.items())
+                          + list(_expr_dims_dbg_sigs.items())):
     fn = getattr(lib, name)
     fn.argtypes = args
     fn.restype = res

@@ -374,6 +374,26 @@ int da_expr_count(const int32_t* prog, int prog_len,
                               DA_EXPR_COUNT, out, st().stream);
 }
 
+int da_expr_reduce_dims(const int32_t* prog, int prog_len,
+                        const uint64_t* dims, int nd,
+                        void* const* srcs, const uint64_t* src_strides,
+                        int nsrcs, const double* consts, int nconsts,
+                        int dtype, uint32_t reduce_mask, int redop,
+                        void* dst) {
+    /* arguments first (host-only), then the init check, as da_scan */
+    ExprDimsPlan pl;
+    int rc = expr_dims_check(prog, prog_len, dims, nd, srcs, src_strides,
+                             nsrcs, consts, nconsts, dtype, reduce_mask,
+                             redop, dst, &pl);
+    if (rc < 0) return rc;
+    DA_REQUIRE_INIT();
+    if (rc == 1) return 0;
+    return launch_expr_reduce_dims(prog, prog_len, dims, nd, srcs,
+                                   src_strides, nsrcs, consts, nconsts,
+                                   dtype, redop, reduce_mask, dst, pl,
+                                   st().stream);
+}
+
 /* 1 = JIT ready (unused yet), 2 = active, -1 = failed (interpreter);
  * DA_EXPR_JIT=0 disables per call.  da_expr_jit_errstr() holds the
  * last hipRTC diagnostic. */
@@ -539,6 +559,16 @@ int dbg_gemm_path(int64_t m, int64_t n, int64_t k) {
 
 int dbg_scan_variant(uint64_t inner, uint64_t axis, uint64_t outer) {
     return scan_variant(inner, axis, outer);
+}
+
+int dbg_expr_dims_variant(const uint64_t* dims, int nd, uint32_t reduce_mask,
+                          uint32_t* nb, uint32_t* gx) {
+    ExprDimsPlan pl;
+    int rc = expr_dims_select(dims, nd, reduce_mask, &pl);
+    if (rc < 0) return rc;
+    if (nb) *nb = pl.nb;
+    if (gx) *gx = pl.gx;
+    return pl.sched;
 }
 
 /* debug-only: how many flat-reduce results were taken from the poll of the

@@ -163,8 +163,8 @@ int launch_expr_jit(const int32_t* prog, int plen, void* dst,
                     int nsrcs, const double* consts, int nconsts,
                     uint64_t n, int dtype, hipStream_t s);
 // Fused mapreduce over a program (kernels_expr.hip): redop is a da_redop,
-// or DA_EXPR_COUNT for the exact count of nonzero terms (out: int64_t).
-constexpr int DA_EXPR_COUNT = -1;
+// or DA_EXPR_COUNT (darray_hip.h) for the exact count of nonzero terms
+// (out: int64_t).
 int validate_expr(const char* who, const int32_t* prog, int plen, int nsrcs,
                   int nconsts);
 int launch_expr_reduce(const int32_t* prog, int plen, const uint64_t* dims,
@@ -180,6 +180,33 @@ int launch_expr_reduce_jit(const int32_t* prog, int plen,
                            const double* consts, int nconsts, uint64_t n,
                            int dtype, int redop, int g, bool fused,
                            hipStream_t s);
+// Fused dims-reduction over a program (kernels_expr.hip, loops in
+// expr_dims_core.hpp).  expr_dims_select is the host-only selector (schedule
+// EDIMS_*, nb slices of `chunk` terms, gridDim.x); expr_dims_check the
+// host-only argument check (0 = launch, 1 = nothing to do, < 0 = error).
+struct ExprDimsPlan {
+    uint64_t K, R;             // outputs; terms folded into each
+    int sched;
+    uint32_t nb, gx, chunk;
+};
+struct ExprDimsArgs;
+int expr_dims_select(const uint64_t* dims, int nd, uint32_t mask,
+                     ExprDimsPlan* pl);
+int expr_dims_check(const int32_t* prog, int plen, const uint64_t* dims,
+                    int nd, void* const* srcs, const uint64_t* src_strides,
+                    int nsrcs, const double* consts, int nconsts, int dtype,
+                    uint32_t mask, int redop, const void* dst,
+                    ExprDimsPlan* pl);
+int launch_expr_reduce_dims(const int32_t* prog, int plen,
+                            const uint64_t* dims, int nd, void* const* srcs,
+                            const uint64_t* src_strides, int nsrcs,
+                            const double* consts, int nconsts, int dtype,
+                            int redop, uint32_t mask, void* dst,
+                            const ExprDimsPlan& pl, hipStream_t s);
+// hipRTC path of the first kernel; 0 / 1 / <0 as launch_expr_jit
+int launch_expr_dims_jit(const int32_t* prog, int plen, int nsrcs, int dtype,
+                         int redop, int sched, const ExprDimsArgs& a,
+                         unsigned int gx, unsigned int nb, hipStream_t s);
 int expr_jit_state();
 const char* expr_jit_err();
 int launch_transpose(void* dst, const void* src, uint64_t m, uint64_t n,

@@ -21,6 +21,7 @@
 // disables the JIT (checked per call — tests toggle it live).
 #include "common.hpp"
 #include "embedded_src.hpp"
+#include "expr_dims_core.hpp"
 #include <hip/hiprtc.h>
 #include <stdlib.h>
 #include <string>
@@ -341,12 +342,45 @@ std::string gen_reduce_source(const int32_t* prog, int plen, int dtype,
     return s;
 }
 
+// Fused dims-reduction kernel for one program: evalx (gen_eval's strided
+// form, unchanged) is the `term` of expr_dims_core.hpp's loops.  The fold
+// (or the count), the schedule, the operand count and the numbers of kept
+// and reduced dimensions after merging — what the reduced mask comes to —
+// are baked in; extents, strides, pointers and constants are arguments.
+std::string gen_dims_source(const int32_t* prog, int plen, int dtype,
+                            int nsrcs, int redop, int sched, int nk, int nr) {
+    const bool count = redop == DA_EXPR_COUNT;
+    const char* tname = dtype == DA_F64 ? "double"
+                        : dtype == DA_F32 ? "float" : "long long";
+    const char* aname = (count || dtype == DA_I64) ? "int64_t" : tname;
+    const int rop = count ? (int)DA_RED_ADD : redop;
+    std::string s =
+        "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n"
+        "#include \"mapops.hpp\"\n#include \"expr_dims_core.hpp\"\n"
+        "typedef da::ExprDimsArgs JArgs;\n";
+    s += gen_eval(prog, plen, tname, dtype == DA_I64, true);
+    char buf[1024];
+    snprintf(buf, sizeof(buf),
+        "/*dims*/extern \"C\" __global__ void "
+        "__launch_bounds__(da::RTPB) ejit(JArgs a) {\n"
+        "  __shared__ %s sh[da::RTPB / 64 + 1];\n"
+        "  da::expr_dims_body<%s, %s, %s, %d, %d, %d, %d>(a, %d,\n"
+        "    [&](const unsigned long long* off) -> %s "
+        "{ return evalx(a, off); }, sh);\n"
+        "}\n",
+        aname, tname, aname, count ? "true" : "false", sched,
+        nsrcs > 0 ? nsrcs : 1, nk, nr, rop, tname);
+    s += buf;
+    return s;
+}
+
 // hipRTC-compile one generated source against the embedded device headers
 // (a pure compiler call: no GPU needed).  0 ok, -1 failure with the
 // diagnostic in g_jit_err; `code` (may be null) receives the code object.
 int jit_compile(const std::string& src, std::vector<char>* code) {
     const char* hdr_names[] = {"stdint.h", "darray_hip.h", "mapops.hpp",
-                               "fastmath.hpp", "reduce_core.hpp"};
+                               "fastmath.hpp", "reduce_core.hpp",
+                               "expr_dims_core.hpp"};
     const char* stdint_stub =
         "#pragma once\n"
         "typedef __INT8_TYPE__ int8_t;\ntypedef __UINT8_TYPE__ uint8_t;\n"
@@ -355,10 +389,11 @@ int jit_compile(const std::string& src, std::vector<char>* code) {
         "typedef __INT64_TYPE__ int64_t;\ntypedef __UINT64_TYPE__ uint64_t;\n";
     const char* hdrs[] = {stdint_stub, embedded_darray_hip_h,
                           embedded_mapops_hpp, embedded_fastmath_hpp,
-                          embedded_reduce_core_hpp};
+                          embedded_reduce_core_hpp,
+                          embedded_expr_dims_core_hpp};
     hiprtcProgram prog;
     hiprtcResult rc = hiprtcCreateProgram(&prog, src.c_str(), "ejit.cu",
-                                          5, hdrs, hdr_names);
+                                          6, hdrs, hdr_names);
     if (rc != HIPRTC_SUCCESS) {
         snprintf(g_jit_err, sizeof(g_jit_err), "hiprtcCreateProgram: %s",
                  hiprtcGetErrorString(rc));
@@ -542,6 +577,32 @@ int launch_expr_reduce_jit(const int32_t* prog, int plen,
     return 0;
 }
 
+// The caller (launch_expr_reduce_dims) has validated everything and sized
+// the partial rows; `a` is passed by value as the kernel's one argument.
+int launch_expr_dims_jit(const int32_t* prog, int plen, int nsrcs, int dtype,
+                         int redop, int sched, const ExprDimsArgs& a,
+                         unsigned int gx, unsigned int nb, hipStream_t s) {
+    const char* e = getenv("DA_EXPR_JIT");
+    if (e && e[0] == '0') return 1;
+    if (g_jit_state < 0) return 1;   // earlier hard failure: interpreter
+    std::string src = gen_dims_source(prog, plen, dtype, nsrcs, redop, sched,
+                                      a.nk, a.nr);
+    hipFunction_t fn;
+    if (jit_get(src, &fn) != 0) {
+        g_jit_state = -1;
+        return 1;
+    }
+    g_jit_state = 2;
+    ExprDimsArgs arg = a;
+    size_t asz = sizeof(arg);
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &arg,
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz,
+                   HIP_LAUNCH_PARAM_END};
+    DA_CHECK_HIP(hipModuleLaunchKernel(fn, gx, nb, 1, RTPB, 1, 1, 0, s,
+                                       nullptr, cfg));
+    return 0;
+}
+
 int expr_jit_state() { return g_jit_state; }
 const char* expr_jit_err() { return g_jit_err; }
 
@@ -581,6 +642,31 @@ extern "C" int dbg_expr_reduce_jit_compile(const int32_t* prog, int plen,
         return -1;
     std::string src = gen_reduce_source(prog, plen, dtype, nd, nsrcs,
                                         strided != 0, redop_or_count);
+    if (src_out && src_len > 0) {
+        strncpy(src_out, src.c_str(), src_len - 1);
+        src_out[src_len - 1] = 0;
+    }
+    return jit_compile(src, nullptr);
+}
+
+/* test-only sibling for the fused dims-reduction kernel: sched is a
+ * da_expr_dims_variant, nk / nr the kept / reduced dimension counts. */
+extern "C" int dbg_expr_dims_jit_compile(const int32_t* prog, int plen,
+                                         int dtype, int nsrcs,
+                                         int redop_or_count, int sched,
+                                         int nk, int nr, char* src_out,
+                                         int src_len) {
+    using namespace da;
+    if (validate_expr("dbg_expr_dims_jit_compile", prog, plen, nsrcs,
+                      DA_EXPR_MAXCONSTS) != 0)
+        return -1;
+    if (redop_or_count < DA_EXPR_COUNT || redop_or_count > DA_RED_MAX ||
+        sched < EDIMS_LANES || sched > EDIMS_BLOCK || nk < 0 ||
+        nk > DA_EXPR_MAXND || nr < 0 || nr > DA_EXPR_MAXND ||
+        (dtype != DA_F64 && dtype != DA_F32 && dtype != DA_I64))
+        return -1;
+    std::string src = gen_dims_source(prog, plen, dtype, nsrcs,
+                                      redop_or_count, sched, nk, nr);
     if (src_out && src_len > 0) {
         strncpy(src_out, src.c_str(), src_len - 1);
         src_out[src_len - 1] = 0;

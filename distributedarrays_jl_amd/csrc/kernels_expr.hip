@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "mapops.hpp"
 #include "reduce_core.hpp"
+#include "expr_dims_core.hpp"
 #include <math.h>
 
 namespace da {
@@ -483,6 +484,273 @@ int launch_expr_reduce(const int32_t* prog, int plen, const uint64_t* dims,
     return reduce_result(out_host, count ? sizeof(int64_t)
                                          : dtype_size(dtype), s,
                          published_seq(fused));
+}
+
+// ---- fused dims-reduction over a program (da_expr_reduce_dims) ---------
+// mapreduce(f, op, A...; dims) with f a broadcast tree: every operand
+// element is read once, nothing of the domain's size is stored.  The loops
+// and the fan-in are expr_dims_core.hpp's, shared with the generated
+// kernels of expr_jit.hip; this interpreter form serves DA_EXPR_JIT=0 and
+// hipRTC failures.  Its evaluator is one out-of-line function per element
+// type: the 18 kernels below would otherwise each inline the functor
+// switch five times.
+template <typename T> struct ExprIsI64 { static constexpr bool v = false; };
+template <> struct ExprIsI64<int64_t> { static constexpr bool v = true; };
+
+template <typename T>
+__device__ __noinline__ T expr_eval_off(const ExprProg& p,
+                                        const unsigned long long* off) {
+    T stack[DA_EXPR_MAXSTACK];
+    int sp = 0;
+    for (int pc = 0; pc < p.len; ++pc) {
+        int ins = p.ins[pc];
+        int kind = ins >> 8, opi = ins & 0xff;
+        switch (kind) {
+        case 1: stack[sp++] = ((const T*)p.srcs[opi])[off[opi]]; break;
+        case 2: stack[sp++] = (T)p.consts[opi]; break;
+        case 0:
+            if constexpr (ExprIsI64<T>::v)
+                stack[sp - 1] = apply_map_i64(opi, stack[sp - 1]);
+            else
+                stack[sp - 1] = apply_map<T>(opi, stack[sp - 1]);
+            break;
+        default: {
+            T b = stack[--sp];
+            if constexpr (ExprIsI64<T>::v)
+                stack[sp - 1] = apply_map2_i64(opi, stack[sp - 1], b);
+            else
+                stack[sp - 1] = apply_map2<T>(opi, stack[sp - 1], b);
+        }
+        }
+    }
+    return stack[0];
+}
+
+template <typename T, typename A, bool COUNT, int SCHED>
+__global__ void __launch_bounds__(RTPB)
+expr_dims_kernel(ExprProg p, ExprDimsArgs a, int redop) {
+    __shared__ A sh[RTPB / 64 + 1];
+    expr_dims_body<T, A, COUNT, SCHED, DA_EXPR_MAXARGS, -1, -1>(
+        a, redop,
+        [&](const unsigned long long* off) -> T {
+            return expr_eval_off<T>(p, off);
+        },
+        sh);
+}
+
+template <typename A>
+__global__ void __launch_bounds__(RTPB)
+expr_dims_fold_kernel(const A* part, A* dst, unsigned int K, unsigned int nb,
+                      int redop) {
+    expr_dims_fold_body<A>(part, dst, K, nb, redop);
+}
+
+namespace {
+constexpr uint32_t EDIMS_SPLIT_BLOCKS = 1024;  // split while fewer workgroups
+constexpr uint32_t EDIMS_MAXBLOCKS = 4096;     // gridDim.x cap (grid-stride)
+
+template <typename T, typename A, bool COUNT>
+hipError_t expr_dims_interp_s(const ExprProg& P, const ExprDimsArgs& a,
+                              int redop, const ExprDimsPlan& pl,
+                              hipStream_t s) {
+    dim3 g(pl.gx, pl.nb), b(RTPB);
+    switch (pl.sched) {
+    case EDIMS_LANES:
+        hipLaunchKernelGGL((expr_dims_kernel<T, A, COUNT, EDIMS_LANES>), g, b,
+                           0, s, P, a, redop);
+        break;
+    case EDIMS_WAVE:
+        hipLaunchKernelGGL((expr_dims_kernel<T, A, COUNT, EDIMS_WAVE>), g, b,
+                           0, s, P, a, redop);
+        break;
+    default:
+        hipLaunchKernelGGL((expr_dims_kernel<T, A, COUNT, EDIMS_BLOCK>), g, b,
+                           0, s, P, a, redop);
+    }
+    return hipGetLastError();
+}
+
+template <typename A>
+hipError_t expr_dims_fold(const void* part, void* dst, uint32_t K,
+                          uint32_t nb, int redop, hipStream_t s) {
+    uint32_t g = (K + RTPB - 1) / RTPB;
+    if (g > EDIMS_MAXBLOCKS) g = EDIMS_MAXBLOCKS;
+    hipLaunchKernelGGL((expr_dims_fold_kernel<A>), dim3(g), dim3(RTPB), 0, s,
+                       (const A*)part, (A*)dst, K, nb, redop);
+    return hipGetLastError();
+}
+}  // namespace
+
+// Host-only: schedule, slices and grid for a chunk shape and a mask of
+// reduced dimensions (exported as dbg_expr_dims_variant).  < 0: bad shape.
+int expr_dims_select(const uint64_t* dims, int nd, uint32_t mask,
+                     ExprDimsPlan* pl) {
+    const char* who = "da_expr_reduce_dims";
+    if (nd < 1 || nd > DA_EXPR_MAXND)
+        return set_err(-3, "%s: nd %d unsupported (1..%d)", who, nd,
+                       DA_EXPR_MAXND);
+    if (!dims) return set_err(-3, "%s: null dims", who);
+    if (mask >> nd)
+        return set_err(-3, "%s: bad mask 0x%x for nd %d", who, mask, nd);
+    uint64_t K = 1, R = 1;
+    bool lead_seen = false, lead_reduced = false;
+    for (int d = 0; d < nd; ++d) {
+        const bool red = (mask >> d) & 1u;
+        uint64_t& acc = red ? R : K;
+        if (dims[d] >> 32 || (acc *= dims[d]) >> 32 || (K * R) >> 32)
+            return set_err(-3, "%s: chunk too large: the index decode needs "
+                           "fewer than 2^32 elements", who);
+        if (!lead_seen && dims[d] > 1) {
+            lead_seen = true;
+            lead_reduced = red;
+        }
+    }
+    pl->K = K;
+    pl->R = R;
+    pl->sched = !lead_reduced ? EDIMS_LANES
+                : R < EDIMS_BLOCK_R ? EDIMS_WAVE : EDIMS_BLOCK;
+    if (K == 0 || R == 0) {      // nothing to launch / identity fill
+        pl->sched = EDIMS_LANES;
+        pl->nb = pl->gx = pl->chunk = 0;
+        return 0;
+    }
+    // outputs per workgroup; fewest terms worth a slice of their own
+    const uint64_t opb = pl->sched == EDIMS_LANES ? RTPB
+                         : pl->sched == EDIMS_WAVE ? RTPB / 64 : 1;
+    const uint64_t minchunk = pl->sched == EDIMS_LANES ? 8
+                              : pl->sched == EDIMS_WAVE ? 256 : 1024;
+    const uint64_t blocks = (K + opb - 1) / opb;
+    uint64_t nb = EDIMS_SPLIT_BLOCKS / blocks;
+    if (nb > R / minchunk) nb = R / minchunk;
+    if (nb < 1) nb = 1;
+    const uint64_t chunk = (R + nb - 1) / nb;
+    pl->chunk = (uint32_t)chunk;
+    pl->nb = (uint32_t)((R + chunk - 1) / chunk);
+    pl->gx = (uint32_t)(blocks < EDIMS_MAXBLOCKS ? blocks : EDIMS_MAXBLOCKS);
+    return 0;
+}
+
+// Host-only argument check of da_expr_reduce_dims: 0 = launch, 1 = nothing
+// to do (no outputs), < 0 = error.  Touches no device memory.
+int expr_dims_check(const int32_t* prog, int plen, const uint64_t* dims,
+                    int nd, void* const* srcs, const uint64_t* src_strides,
+                    int nsrcs, const double* consts, int nconsts, int dtype,
+                    uint32_t mask, int redop, const void* dst,
+                    ExprDimsPlan* pl) {
+    const char* who = "da_expr_reduce_dims";
+    if (!prog) return set_err(-3, "%s: null prog", who);
+    int rc = validate_expr(who, prog, plen, nsrcs, nconsts);
+    if (rc) return rc;
+    if (redop != DA_EXPR_COUNT && (redop < 0 || redop > DA_RED_MAX))
+        return set_err(-3, "%s: bad redop %d", who, redop);
+    if (dtype != DA_F64 && dtype != DA_F32 && dtype != DA_I64)
+        return set_err(-3, "%s: bad dtype %d", who, dtype);
+    if (nsrcs > 0 && !srcs) return set_err(-3, "%s: null srcs", who);
+    if (nconsts > 0 && !consts) return set_err(-3, "%s: null consts", who);
+    // the size limit comes before anything that could reach the JIT
+    rc = expr_dims_select(dims, nd, mask, pl);
+    if (rc) return rc;
+    if (src_strides)
+        for (int i = 0; i < nsrcs * nd; ++i)
+            if (src_strides[i] >> 32)
+                return set_err(-3, "%s: stride %d too large", who, i);
+    if (pl->K == 0) return 1;
+    if (!dst) return set_err(-3, "%s: null dst", who);
+    return 0;
+}
+
+int launch_expr_reduce_dims(const int32_t* prog, int plen,
+                            const uint64_t* dims, int nd, void* const* srcs,
+                            const uint64_t* src_strides, int nsrcs,
+                            const double* consts, int nconsts, int dtype,
+                            int redop, uint32_t mask, void* dst,
+                            const ExprDimsPlan& pl, hipStream_t s) {
+    const bool count = redop == DA_EXPR_COUNT;
+    const int rop = count ? (int)DA_RED_ADD : redop;
+    const bool acc64 = count || dtype == DA_I64;   // int64 accumulator
+    const uint32_t K = (uint32_t)pl.K;
+    auto fold = [&](const void* part, uint32_t nb) {
+        if (acc64) return expr_dims_fold<int64_t>(part, dst, K, nb, rop, s);
+        if (dtype == DA_F64)
+            return expr_dims_fold<double>(part, dst, K, nb, rop, s);
+        return expr_dims_fold<float>(part, dst, K, nb, rop, s);
+    };
+    if (pl.R == 0) {   // an empty fold: the identity (0 for a count)
+        DA_CHECK_HIP(fold(nullptr, 0));
+        return 0;
+    }
+
+    // kept / reduced dimension lists: extents of 1 dropped, neighbours
+    // merged where every operand's stride lets one index run across both
+    ExprDimsArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nsrcs; ++i) a.srcs[i] = srcs[i];
+    for (int i = 0; i < nconsts; ++i) a.consts[i] = consts[i];
+    a.K = K;
+    a.R = (uint32_t)pl.R;
+    a.chunk = pl.chunk;
+    uint64_t dense = 1;
+    for (int d = 0; d < nd; ++d) {
+        uint32_t str[DA_EXPR_MAXARGS];
+        for (int k = 0; k < nsrcs; ++k)
+            str[k] = (uint32_t)(src_strides ? src_strides[(size_t)k * nd + d]
+                                            : dense);
+        dense *= dims[d];
+        if (dims[d] == 1) continue;
+        const bool red = (mask >> d) & 1u;
+        int& n = red ? a.nr : a.nk;
+        uint32_t* ext = red ? a.rext : a.kext;
+        uint32_t (*st_)[DA_EXPR_MAXND] = red ? a.rstr : a.kstr;
+        bool merge = n > 0;
+        for (int k = 0; merge && k < nsrcs; ++k)
+            merge = (uint64_t)st_[k][n - 1] * ext[n - 1] == str[k];
+        if (merge) {
+            ext[n - 1] *= (uint32_t)dims[d];
+        } else {
+            ext[n] = (uint32_t)dims[d];
+            for (int k = 0; k < nsrcs; ++k) st_[k][n] = str[k];
+            ++n;
+        }
+    }
+
+    void* out = dst;
+    if (pl.nb > 1) {
+        int rc = ensure_partials((size_t)pl.nb * K * sizeof(double));
+        if (rc) return rc;
+        out = st().partials;
+    }
+    a.dst = out;
+
+    int rc = launch_expr_dims_jit(prog, plen, nsrcs, dtype, redop, pl.sched,
+                                  a, pl.gx, pl.nb, s);
+    if (rc < 0) return rc;
+    if (rc == 1) {   // interpreter (DA_EXPR_JIT=0 or hipRTC failed)
+        ExprProg P;
+        memset(&P, 0, sizeof(P));
+        for (int i = 0; i < plen; ++i) P.ins[i] = prog[i];
+        P.len = plen;
+        for (int i = 0; i < nsrcs; ++i) P.srcs[i] = srcs[i];
+        for (int i = 0; i < nconsts; ++i) P.consts[i] = consts[i];
+        hipError_t he;
+        if (dtype == DA_I64)
+            he = count ? expr_dims_interp_s<int64_t, int64_t, true>(P, a, rop,
+                                                                    pl, s)
+                       : expr_dims_interp_s<int64_t, int64_t, false>(
+                             P, a, rop, pl, s);
+        else if (dtype == DA_F64)
+            he = count ? expr_dims_interp_s<double, int64_t, true>(P, a, rop,
+                                                                   pl, s)
+                       : expr_dims_interp_s<double, double, false>(P, a, rop,
+                                                                   pl, s);
+        else
+            he = count ? expr_dims_interp_s<float, int64_t, true>(P, a, rop,
+                                                                  pl, s)
+                       : expr_dims_interp_s<float, float, false>(P, a, rop,
+                                                                 pl, s);
+        DA_CHECK_HIP(he);
+    }
+    if (pl.nb > 1) DA_CHECK_HIP(fold(out, pl.nb));
+    return 0;
 }
 
 } // namespace da

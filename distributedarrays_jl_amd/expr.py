@@ -252,13 +252,14 @@ def _validate(dest, prog, args, consts):
                                   "representable" % c)
 
 
-def _localize(dest, args):
+def _localize(dest, args, i64_strided=False):
     """Per-operand localisation onto dest's chunk boxes (bclocal /
     makelocal, broadcast.jl:140-152 + _bcview :103-120), shared by
     materialize_ and the fused reductions.  `dest` only supplies
     geometry (dims, idxs, ranks, lshape).  An operand with dest's exact
     layout contributes its own chunk pointer; any other is projected
     through gather_box (singleton dims clamp to (0, 1) and get stride 0).
+    i64_strided: the caller's kernel takes strides for i64 too.
     Returns (flat, ptrs, strides, bufs); the caller frees bufs."""
     from .ops import gather_box, _same_layout
 
@@ -267,7 +268,7 @@ def _localize(dest, args):
     aligned = [full[i] and _same_layout(dest, a)
                for i, a in enumerate(args)]
     flat = all(aligned)
-    if not flat and dest.dtype == "i64":
+    if not flat and dest.dtype == "i64" and not i64_strided:
         raise DArrayError("expr: i64 supports only aligned full-shape "
                           "operands (strided variant is float-only)")
 
@@ -425,7 +426,65 @@ def _fused(e, op):
     return out.value
 
 
-def reduce(op, e):
+def _fused_dims(e, op, dims):
+    """One da_expr_reduce_dims call over this rank's chunk of the broadcast
+    domain (op a fold name, or None to count), then the cross-chunk combine
+    of dreduce_dims: partial slabs travel to the lowest-coordinate owners
+    and are folded in ascending source rank.  Returns the result DArray."""
+    from . import ops
+    from ._ffi import EXPR_COUNT
+    from ._opcodes import DTYPE_SIZE
+    prog, args, consts = compile_expr(e)
+    gdims, dom = _domain(args)
+    if dom is None:
+        from .darray import DArray
+        dom = DArray(gdims, args[0].dtype, _alloc=False)
+    _validate(dom, prog, args, consts)
+    nd = dom.ndims
+    if nd > MAXND:
+        raise DArrayError("expr: ndims %d > %d" % (nd, MAXND))
+    dims = ops._norm_dims("expr.reduce", dims, nd)
+    if dom.ranks != list(range(dom.nchunks)):
+        raise DArrayError("expr.reduce: with dims the domain must have "
+                          "identity ranks")
+    rdtype, rop = ("i64", "add") if op is None else (dom.dtype, op)
+    R = ops._dims_result(dom, dims, rdtype)
+    partial = pshape = None
+    bufs = []
+    try:
+        flat, ptrs, strides, bufs = _localize(dom, args, i64_strided=True)
+        if dom.lchunk is not None:
+            pshape = tuple(1 if a in dims else dom.lshape[a]
+                           for a in range(nd))
+            partial = ops._Buf(max(ops.d2_numel(pshape), 1)
+                               * DTYPE_SIZE[rdtype])
+            parr, dims_arr, src_arr, sarr, cons_arr = _program_args(
+                dom, prog, consts, flat, ptrs, strides)
+            mask = 0
+            for a in dims:
+                mask |= 1 << a
+            # empty chunks call in too: no outputs launches nothing, an
+            # empty reduced extent gives the fold identity / zero count
+            check(lib.da_expr_reduce_dims(
+                parr, len(prog), dims_arr, nd, src_arr, sarr, len(args),
+                cons_arr, len(consts), DTYPES[dom.dtype], mask,
+                EXPR_COUNT if op is None else RED_OPS[op], partial.p))
+        part, partial = partial, None
+        # frees `part` and drains the stream: the gathered operands are
+        # free to go afterwards
+        return ops._dims_combine(dom, dims, R, part, pshape, rop)
+    except BaseException:
+        if partial is not None:
+            partial.free()
+        R.close()
+        raise
+    finally:
+        for b in bufs:
+            if b is not None:
+                b.free()
+
+
+def reduce(op, e, dims=None):
     """mapreduce(f, op, A...) with f given as a broadcast tree
     (mapreduce.jl:29-35), fused: every operand element is read once and
     nothing is materialised.  op is add, mul, min or max; returns a
@@ -434,16 +493,29 @@ def reduce(op, e):
 
         E.reduce("add", E.ref(x) * E.ref(y))          # dot, one pass
         E.reduce("add", E.abs2(E.ref(a) - E.ref(b)))  # sum(abs2, a .- b)
+
+    With dims (an int or an iterable of 0-based dimensions) the fold runs
+    along those dimensions only — mapreduce(f, op, A...; dims),
+    mapreduce.jl:83-94 — still in one pass per chunk, and the result is a
+    DArray: reduced dims have size 1 (Julia keepdims) and grid 1, chunks
+    on the lowest-coordinate owners, as dreduce_dims places them.
+
+        E.reduce("add", E.abs2(E.ref(X) - E.ref(mu)), dims=0)
     """
     if op not in RED_OPS:
         raise DArrayError("expr: unknown reduction %r" % (op,))
+    if dims is not None:
+        return _fused_dims(wrap(e), op, dims)
     return _fused(wrap(e), op)
 
 
-def count(e):
+def count(e, dims=None):
     """count(!iszero, bc): the exact number of nonzero elements of the
     tree's values (a NaN counts), as an int.  Predicates are comparison
     trees, e.g. E.count(E.ref(x) > c) or E.count(E.eq(a, b)): IEEE for
     floats (a comparison with NaN is false, except ne), exact signed
-    comparison for i64.  Collective."""
+    comparison for i64.  Collective.  With dims: the counts along those
+    dimensions as an i64 DArray, laid out as reduce's."""
+    if dims is not None:
+        return _fused_dims(wrap(e), None, dims)
     return int(_fused(wrap(e), None))

@@ -244,7 +244,7 @@ def _tree(f, ds):
     return e
 
 
-def mapreduce(f, op, d, *more):
+def mapreduce(f, op, d, *more, dims=None):
     """mapreduce(f, op, d) — mapreduce.jl:29-35: per-chunk kernel
     reduction, then the cross-worker fold as one scalar RCCL allreduce
     (tree; partials are 8 bytes — latency-bound).
@@ -253,12 +253,19 @@ def mapreduce(f, op, d, *more):
     of each array and returns a broadcast tree, which is reduced fused
     (expr.reduce: one pass, no temporary) — mapreduce(t -> t*t, +, D)
     is mapreduce(lambda t: t * t, "add", D), and Julia's multi-array
-    mapreduce(f, op, A, B) passes the further arrays after d."""
+    mapreduce(f, op, A, B) passes the further arrays after d.
+
+    dims (an int or an iterable of 0-based dimensions) reduces along
+    those dimensions only and returns a DArray with them of size 1: a
+    callable f fused in one pass (expr.reduce with dims), a name through
+    dreduce_dims."""
     if callable(f):
         from . import expr as E
-        return E.reduce(op, _tree(f, (d,) + more))
+        return E.reduce(op, _tree(f, (d,) + more), dims=dims)
     if more:
         raise DArrayError("mapreduce: several arrays need a callable f")
+    if dims is not None:
+        return dreduce_dims(f, op, d, dims)
     out = _local_reduce(f, op, d)
     if d.nranks > 1:
         check(lib.da_allreduce(ctypes.byref(out), 1, DTYPES[d.dtype],
@@ -623,25 +630,21 @@ def dmatmul(A, B, alpha=1.0):
 _RED2MAP2 = {"add": "add", "mul": "mul", "min": "min2", "max": "max2"}
 
 
-def dreduce_dims(f, op, d, dims):
-    """mapreduce(f, op, D; dims=dims) — src/mapreduce.jl:42-94:
-    per-chunk kernel reduction (mapreducedim_within), then cross-chunk
-    combine onto the lowest-coordinate slab owners
-    (reducedim_initarray stores R on A.pids[region -> 1:1],
-    mapreducedim_between! pulls co-slabs and folds; here: grouped
-    ncclSend/Recv of partial slabs + ascending-source-rank elementwise
-    combine).  Result keeps reduced dims as size 1 (Julia keepdims)."""
+def _norm_dims(who, dims, nd):
+    """dims as a sorted, de-duplicated tuple of 0-based dimensions."""
     if isinstance(dims, int):
         dims = (dims,)
     dims = tuple(sorted(set(int(a) for a in dims)))
-    nd = d.ndims
     if any(a < 0 or a >= nd for a in dims):
-        raise DArrayError("dreduce_dims: bad dims %r" % (dims,))
-    if d.ranks != list(range(d.nchunks)):
-        raise DArrayError("dreduce_dims: source must have identity ranks")
-    dt = DTYPES[d.dtype]
-    esz = DTYPE_SIZE[d.dtype]
+        raise DArrayError("%s: bad dims %r" % (who, dims))
+    return dims
 
+
+def _dims_result(d, dims, dtype):
+    """The DArray a reduction of d's domain along dims lands in: reduced
+    dims have size 1 and grid 1, chunks live on the lowest-coordinate
+    owners (reducedim_initarray: A.pids[region -> 1:1])."""
+    nd = d.ndims
     rdims = tuple(1 if a in dims else d.dims[a] for a in range(nd))
     rdist = tuple(1 if a in dims else d.dist[a] for a in range(nd))
     # owner of R chunk c = D-grid rank with reduced coords 0
@@ -652,7 +655,24 @@ def dreduce_dims(f, op, d, dims):
     for lin in range(nr_chunks):
         sub = list(geometry.grid_pos(lin, rdist))
         owners.append(geometry.grid_rank(sub, d.dist))
-    R = DArray(rdims, d.dtype, rdist, ranks=owners)
+    return DArray(rdims, dtype, rdist, ranks=owners)
+
+
+def dreduce_dims(f, op, d, dims):
+    """mapreduce(f, op, D; dims=dims) — src/mapreduce.jl:42-94:
+    per-chunk kernel reduction (mapreducedim_within), then cross-chunk
+    combine onto the lowest-coordinate slab owners
+    (reducedim_initarray stores R on A.pids[region -> 1:1],
+    mapreducedim_between! pulls co-slabs and folds; here: grouped
+    ncclSend/Recv of partial slabs + ascending-source-rank elementwise
+    combine).  Result keeps reduced dims as size 1 (Julia keepdims)."""
+    nd = d.ndims
+    dims = _norm_dims("dreduce_dims", dims, nd)
+    if d.ranks != list(range(d.nchunks)):
+        raise DArrayError("dreduce_dims: source must have identity ranks")
+    dt = DTYPES[d.dtype]
+    esz = DTYPE_SIZE[d.dtype]
+    R = _dims_result(d, dims, d.dtype)
 
     me = d.rank
     partial = None
@@ -684,6 +704,17 @@ def dreduce_dims(f, op, d, dims):
         partial = cur
         pshape = tuple(shape)
 
+    return _dims_combine(d, dims, R, partial, pshape, op)
+
+
+def _dims_combine(d, dims, R, partial, pshape, op):
+    """Cross-chunk step of a dims-reduction over d's grid: every rank with
+    a chunk holds `partial` (a _Buf of pshape elements of R's dtype, freed
+    here); the co-slabs travel to R's owners in one grouped send/recv and
+    are folded there with `op` in ascending source rank."""
+    me = d.rank
+    dt = DTYPES[R.dtype]
+    esz = DTYPE_SIZE[R.dtype]
     # exchange: group D-ranks by owner (ascending rank == ascending
     # column-major reduced coords, the co-slab concatenation order of
     # mapreducedim_between!, mapreduce.jl:71-81)
@@ -774,6 +805,88 @@ def dmean_dims(d, dims):
         nred *= d.dims[a]
     scale_(R, 1.0 / nred)
     return R
+
+
+def _nreduced(d, dims):
+    n = 1
+    for a in dims:
+        n *= d.dims[a]
+    return n
+
+
+def dvar_dims(d, dims, corrected=True):
+    """var(D; dims, corrected): two passes, no temporary of D's size —
+    dmean_dims, then the fused sum(abs2, D .- mean; dims) with the mean
+    broadcast through its singleton dims (expr.reduce with dims).  Float
+    arrays only; NaN where the denominator is not positive."""
+    if d.dtype == "i64":
+        raise DArrayError("dvar_dims: float arrays only (dcast first)")
+    dims = _norm_dims("dvar_dims", dims, d.ndims)
+    nred = _nreduced(d, dims)
+    den = nred - 1 if corrected else nred
+    if nred == 0:
+        if d.ranks != list(range(d.nchunks)):
+            raise DArrayError("dvar_dims: source must have identity ranks")
+        R = _dims_result(d, dims, d.dtype)
+        R.fill_(float("nan"))
+        return R
+    from . import expr as E
+    M = dmean_dims(d, dims)
+    try:
+        S = E.reduce("add", E.abs2(E.ref(d) - E.ref(M)), dims=dims)
+    finally:
+        M.close()
+    if den > 0:
+        return map2_scalar_("div", S, S, float(den))
+    S.fill_(float("nan"))
+    return S
+
+
+def dstd_dims(d, dims, corrected=True):
+    """std(D; dims, corrected): sqrt of dvar_dims."""
+    S = dvar_dims(d, dims, corrected)
+    return map_("sqrt", S, S)
+
+
+def _pred_tree(pred, d):
+    """The broadcast tree whose nonzero values a predicate counts."""
+    from . import expr as E
+    if callable(pred):
+        return _tree(pred, (d,))
+    if pred not in _PREDICATES:
+        raise DArrayError("%r is not a predicate" % (pred,))
+    x = E.ref(d)
+    if pred == "nonzero":
+        return x
+    if d.dtype == "i64":        # an integer is never NaN, always finite
+        return E.ne(x, x) if pred == "isnan" else E.eq(x, x)
+    return E.Unary(pred, x)
+
+
+def dcount_dims(pred, d, dims):
+    """count(pred, D; dims): an i64 DArray (reduced dims of size 1) of the
+    exact number of elements along dims at which pred holds.  pred is a
+    predicate name (nonzero, isnan, isfinite) or a callable building a
+    broadcast tree, e.g. lambda x: x > 0.5; fused, one pass."""
+    from . import expr as E
+    return E.count(_pred_tree(pred, d), dims=dims)
+
+
+def dall_dims(pred, d, dims):
+    """all(pred, D; dims): an i64 DArray of 1 / 0 (the mask convention);
+    1 where nothing is reduced over."""
+    from . import expr as E
+    dims = _norm_dims("dall_dims", dims, d.ndims)
+    C = dcount_dims(pred, d, dims)
+    return E.materialize_(C, E.eq(E.ref(C), _nreduced(d, dims)))
+
+
+def dany_dims(pred, d, dims):
+    """any(pred, D; dims): an i64 DArray of 1 / 0; 0 where nothing is
+    reduced over."""
+    from . import expr as E
+    C = dcount_dims(pred, d, dims)
+    return E.materialize_(C, E.ref(C) > 0)
 
 
 # ---------------------------------------------------------- prefix scans

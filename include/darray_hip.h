@@ -218,6 +218,29 @@ int da_expr_count(const int32_t* prog, int prog_len,
                   void* const* srcs, const uint64_t* src_strides, int nsrcs,
                   const double* consts, int nconsts, uint64_t n, int dtype,
                   int64_t* out);
+/* Fused mapreduce ALONG DIMENSIONS over a program — mapreduce(f, op, A...;
+ * dims) with f a broadcast tree (mapreduce.jl:83-94): one pass for any set
+ * of reduced dimensions, one read per operand element, no temporary of the
+ * chunk's size.  Program arguments as da_expr_reduce.  dims[nd] is the
+ * local chunk shape (column-major, nd <= DA_EXPR_MAXND, fewer than 2^32
+ * elements in all); bit d of reduce_mask set = dimension d is reduced.
+ * src_strides as da_expr (NULL = every operand dense over the chunk); all
+ * of f64 / f32 / i64 take strides here.  redop is a da_redop, or
+ * DA_EXPR_COUNT for the exact count of nonzero terms.  dst is DEVICE
+ * memory of K = prod(kept extents) elements in column-major order of the
+ * kept dimensions: the operand dtype for a fold, int64_t for a count.
+ * K == 0 launches nothing; a reduced extent of 0 fills dst with the fold
+ * identity (0 for a count).  Stream-ordered, no host synchronisation.
+ * The result's bits depend on the shape, the mask and the program alone:
+ * fixed fold order, no atomics, the same through hipRTC and DA_EXPR_JIT=0
+ * (DESIGN.md §17).  Arguments are checked before the da_init check. */
+#define DA_EXPR_COUNT (-1)
+int da_expr_reduce_dims(const int32_t* prog, int prog_len,
+                        const uint64_t* dims, int nd,
+                        void* const* srcs, const uint64_t* src_strides,
+                        int nsrcs, const double* consts, int nconsts,
+                        int dtype, uint32_t reduce_mask, int redop,
+                        void* dst);
 int da_map2_scalar(int opcode, void* dst, const void* src, double c,
                    int reverse, uint64_t n, int dtype);      /* D .+ 1 etc (scalar broadcast arg, broadcast.jl:124-133) */
 int da_axpby(void* y, const void* x, double alpha, double beta,
@@ -409,6 +432,19 @@ int dbg_gemm_path(int64_t m, int64_t n, int64_t k);
  * `extern int`: tests/test_abi.py pins the set of plain `int dbg_*`
  * declarations to the two selectors above) */
 extern int dbg_scan_variant(uint64_t inner, uint64_t axis, uint64_t outer);
+/* lanes: the leading dimension (the first of extent > 1) is kept, a thread
+ * per output; wave / block: it is reduced, a wave (fewer than 512 terms per
+ * output) or a workgroup per output */
+enum da_expr_dims_variant { DA_EDIMS_LANES = 0, DA_EDIMS_WAVE,
+                            DA_EDIMS_BLOCK };
+/* schedule da_expr_reduce_dims picks for a chunk shape and mask (< 0: a
+ * shape or mask it rejects); *nb = slices the reduced index space is split
+ * into (> 1: partial rows and a second fold kernel; 0: no term to fold),
+ * *gx = workgroups along x of the first launch (capped; grid-stride
+ * beyond).  Either pointer may be NULL.  (`extern int`: see above) */
+extern int dbg_expr_dims_variant(const uint64_t* dims, int nd,
+                                 uint32_t reduce_mask, uint32_t* nb,
+                                 uint32_t* gx);
 /* how many scalar results (da_reduce, da_count, da_expr_reduce,
  * da_expr_count) were taken from the poll of the pinned slot and how many
  * from the stream-sync fallback since da_init; either pointer may be NULL */
