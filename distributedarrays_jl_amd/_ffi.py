@@ -26,6 +26,32 @@ try:
     ctypes.CDLL("/opt/rocm/lib/libamdhip64.so", mode=ctypes.RTLD_GLOBAL)
 except OSError:
     pass
+# The same for the code-object manager.  hipRTC opens "libamd_comgr.so.3"
+# by name on its first compile and the loader hands it the first object
+# of that soname in the process.  If that is torch's bundled copy, its
+# OCML is not the one hipcc linked into libdarray_hip.so and the expr JIT
+# stops giving da_map's bits (measured: tgamma 2 ulp apart).  Importing
+# this package before torch pins the ROCm copy; after torch it is too
+# late, and all that is left is to say so.
+try:
+    with open("/proc/self/maps") as _maps:
+        _foreign = sorted({_l.split()[-1] for _l in _maps
+                           if "libamd_comgr" in _l
+                           and "/opt/rocm" not in _l})
+    if _foreign:
+        import warnings
+        warnings.warn(
+            "%s was loaded before distributedarrays_jl_amd: hipRTC will "
+            "compile the expr JIT kernels with it, and their results can "
+            "differ in the last bits from the library's own kernels. "
+            "Import distributedarrays_jl_amd before torch."
+            % _foreign[0], RuntimeWarning, stacklevel=2)
+except OSError:
+    pass
+try:
+    ctypes.CDLL("/opt/rocm/lib/libamd_comgr.so.3", mode=ctypes.RTLD_GLOBAL)
+except OSError:
+    pass
 
 lib = ctypes.CDLL(_SO)
 

@@ -5,14 +5,22 @@
 // 6.3 TB/s copy ceiling): OCML always runs its large-argument-capable
 // path.  These routines restate the classic fdlibm algorithms
 // (Sun Microsystems 1993, public; the basis of glibc/musl libm):
-//   - sin/cos: 2-step Cody-Waite pi/2 reduction (exact for |n| < 2^20,
-//     i.e. |x| < ~1.6e6) + the 13/14-degree minimax kernel polynomials
-//     with the double-double tail carried through (k_sin/k_cos);
+//   - sin/cos: Cody-Waite pi/2 reduction, two steps and a third for
+//     arguments within 2^-49 |x| of a multiple of pi/2 (exact products for
+//     |n| < 2^20, i.e. |x| < ~1.6e6) + the 13/14-degree minimax kernel
+//     polynomials with the double-double tail carried through
+//     (k_sin/k_cos);
 //   - exp: ln2 Cody-Waite reduction + the degree-5 rational kernel.
-// Accuracy < 1 ulp on the fast range (parity-tested at 1e-13 rel vs
-// numpy/libm, tests/test_gpu_parity.py).  Arguments outside the fast
-// range (|x| >= 1e6 for sin/cos, |x| >= 708 for exp, NaN/Inf) fall
-// back to OCML — correctness everywhere, speed where the data lives.
+// Accuracy against the TRUE value (mpmath), on the fast range: sin 0.79,
+// cos 0.77, exp 0.82 ulp worst over a signed log-uniform + uniform sweep
+// of [2^-30, 1e6) (exp: |x| < 708), 0.50 ulp on the doubles nearest
+// n*pi/2 (n <= 4096, and the 4096 closest below 1e6), all switch points
+// (pi/4, 0.3, 0.78125, 2^-27, 2^-28) included.  tests/fastmath_model.py
+// restates this file in numpy; the device gives its bits
+// (tests/test_gpu_math_ulp.py) and the model is held to <= 1 ulp
+// (tests/test_fastmath_model.py).  Arguments outside the fast range
+// (|x| >= 1e6 for sin/cos, |x| >= 708 for exp, NaN/Inf) fall back to
+// OCML — correctness everywhere, speed where the data lives.
 // Uniform-input workloads (drand chunks) take the fast path on every
 // lane, so there is no divergence.
 //
@@ -50,31 +58,45 @@ __device__ __forceinline__ double k_cos(double x, double y) {
     double z = x * x;
     double r = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
     double ax = fabs(x);
-    // qx staves off cancellation in 1 - z/2 (0.25*ax is an exact op)
-    double qx = (ax > 0.3) ? ((ax > 0.78125) ? 0.28125 : 0.25 * ax) : 0.0;
+    // qx ~ |x|/4 staves off cancellation in 1 - z/2.  It is cut to its
+    // high 32 bits (as fdlibm does) so that a = 1 - qx below is EXACT;
+    // with all 53 bits kept a rounds and the result reaches 1.3 ulp.
+    double qx = 0.0;
+    if (ax > 0.3)
+        qx = (ax > 0.78125)
+                 ? 0.28125
+                 : __hiloint2double(__double2hiint(0.25 * ax), 0);
     double hz = 0.5 * z - qx;
     double a = 1.0 - qx;
     return a - (hz - (z * r - x * y));
 }
 
-// ---- 2-step Cody-Waite reduction x -> (y0, y1), quadrant n (mod 4).
-// pio2_1 carries 33 bits, so fn*pio2_1 is exact for |fn| < 2^20;
-// the second step leaves y0+y1 with ~86 good bits.
+// ---- Cody-Waite reduction x -> (y0, y1), quadrant n (mod 4).
+// pio2_1, pio2_2 and pio2_3 carry 33 bits each, so fn*pio2_k is exact
+// for |fn| < 2^20.  Two steps use pi/2 to ~118 bits: enough unless x
+// lies so close to a multiple of pi/2 that y0 cancels by more than
+// 49 bits.  Those rare lanes take fdlibm's third step (~151 bits).
 __device__ __forceinline__ int rem_pio2_medium(double x, double& y0,
                                                double& y1) {
     const double invpio2 = 6.36619772367581382433e-01;
     const double pio2_1 = 1.57079632673412561417e+00;
-    const double pio2_1t = 6.07710050650619224932e-11;
     const double pio2_2 = 6.07710050630396597660e-11;
     const double pio2_2t = 2.02226624879595063154e-21;
+    const double pio2_3 = 2.02226624871116645580e-21;
+    const double pio2_3t = 8.47842766036889956997e-32;
     double fn = rint(x * invpio2);
-    double r = x - fn * pio2_1;
-    double w = fn * pio2_1t;
-    double t = r;
-    w = fn * pio2_2;
-    r = t - w;
+    double t = x - fn * pio2_1;
+    double w = fn * pio2_2;
+    double r = t - w;
     w = fn * pio2_2t - ((t - r) - w);
     y0 = r - w;
+    if (fabs(y0) * 562949953421312.0 < fabs(x)) {   // |y0|*2^49 < |x|
+        t = r;
+        w = fn * pio2_3;
+        r = t - w;
+        w = fn * pio2_3t - ((t - r) - w);
+        y0 = r - w;
+    }
     y1 = (r - y0) - w;
     return ((int)fn) & 3;
 }

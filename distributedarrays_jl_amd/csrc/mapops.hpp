@@ -4,7 +4,7 @@
 // numerics: da_expr of a single-op program is bit-identical to da_map.
 //
 // Semantics follow the reference's scalar-math list
-// (/root/reference/test/darray.jl:775-800) with Julia conventions
+// (test/darray.jl:775-800) with Julia conventions
 // (sign/round/sinc/cosc/mod noted inline); compiled -ffp-contract=off.
 #pragma once
 #include "darray_hip.h"
@@ -24,6 +24,27 @@ template <> struct MathF<double> {
     static __device__ double sqrt_(double x) { return sqrt(x); }
 };
 
+// OCML is within a few ulp on these four but does not keep the IEEE-754
+// (and Julia) sign of a zero result, nor the sign of a tiny argument:
+// expm1(-0) and log1p(-0) came back +0, log1p(-5e-324) +0, sinpi(n) as
+// (-1)^n * 0 and cospi(n + 1/2) as -0 for some n.  Below 1e-20 both
+// expm1(x) and log1p(x) round to x in either precision (the next term,
+// x*x/2, is under 2^-66 x); a NaN takes the same exit unchanged.
+template <typename T> __device__ __forceinline__ T da_expm1(T x) {
+    return !(fabs(x) >= (T)1e-20) ? x : expm1(x);
+}
+template <typename T> __device__ __forceinline__ T da_log1p(T x) {
+    return !(fabs(x) >= (T)1e-20) ? x : log1p(x);
+}
+template <typename T> __device__ __forceinline__ T da_sinpi(T x) {
+    T r = sinpi(x);
+    return r == (T)0 ? copysign((T)0, x) : r;   // sinpi(+-n) = +-0
+}
+template <typename T> __device__ __forceinline__ T da_cospi(T x) {
+    T r = cospi(x);
+    return r == (T)0 ? (T)0 : r;                // cospi(n + 1/2) = +0
+}
+
 template <typename T>
 __device__ __forceinline__ T apply_map(int op, T x) {
     const T one = (T)1, zero = (T)0;
@@ -39,11 +60,11 @@ __device__ __forceinline__ T apply_map(int op, T x) {
     case DA_OP_EXP: return da_exp(x);
     case DA_OP_EXP2: return exp2(x);
     case DA_OP_EXP10: return pow((T)10, x);
-    case DA_OP_EXPM1: return expm1(x);
+    case DA_OP_EXPM1: return da_expm1(x);
     case DA_OP_LOG: return log(x);
     case DA_OP_LOG2: return log2(x);
     case DA_OP_LOG10: return log10(x);
-    case DA_OP_LOG1P: return log1p(x);
+    case DA_OP_LOG1P: return da_log1p(x);
     case DA_OP_SIN: return da_sin(x);
     case DA_OP_COS: return da_cos(x);
     case DA_OP_TAN: return tan(x);
@@ -56,8 +77,8 @@ __device__ __forceinline__ T apply_map(int op, T x) {
     case DA_OP_ASINH: return asinh(x);
     case DA_OP_ACOSH: return acosh(x);
     case DA_OP_ATANH: return atanh(x);
-    case DA_OP_SINPI: return sinpi(x);
-    case DA_OP_COSPI: return cospi(x);
+    case DA_OP_SINPI: return da_sinpi(x);
+    case DA_OP_COSPI: return da_cospi(x);
     case DA_OP_FLOOR: return floor(x);
     case DA_OP_CEIL: return ceil(x);
     case DA_OP_ROUND: return rint(x);   // Julia round = half-even
@@ -77,7 +98,7 @@ __device__ __forceinline__ T apply_map(int op, T x) {
     case DA_OP_GAMMA: return tgamma(x);
     case DA_OP_LGAMMA: return lgamma(x);
     case DA_OP_SINC:   // Julia sinc: sin(pi x)/(pi x), 1 at 0
-        return x == zero ? one : sinpi(x) / ((T)M_PI * x);
+        return x == zero ? one : da_sinpi(x) / ((T)M_PI * x);
     case DA_OP_COSC:   // Julia cosc: d/dx sinc = cospi(x)/x - sinpi(x)/(pi x^2)
         return x == zero ? zero
                          : cospi(x) / x - sinpi(x) / ((T)M_PI * x * x);
@@ -127,7 +148,11 @@ __device__ __forceinline__ T apply_map2(int op, T a, T b) {
     case DA_OP2_REM: return fmod(a, b);
     case DA_OP2_MOD: {   // floored (Julia mod / numpy mod)
         T r = fmod(a, b);
-        if (r != (T)0 && ((r < (T)0) != (b < (T)0))) r += b;
+        if (r != (T)0) {
+            if ((r < (T)0) != (b < (T)0)) r += b;
+        } else {
+            r = copysign((T)0, b);   // a zero takes the divisor's sign
+        }
         return r;
     }
     case DA_OP2_POW: return pow(a, b);

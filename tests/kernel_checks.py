@@ -136,6 +136,35 @@ def check_sum_in_bound(dja, dt, n, seed):
         d.close()
 
 
+# ---------------------------------------------------------------- map math
+def check_map_ulp(dja, n=2000):
+    """f64 sin/cos/exp through da_map on a small hard vector (specials at
+    both ends, length = 3 mod 4): <= 1 ulp against mpmath on the fast
+    range and the bits of the CPU model.  Run under DA_MAP_W=2 by
+    variant_child, this covers the vector-of-2 kernels; the full sweep is
+    in test_gpu_math_ulp."""
+    import fastmath_model as fm
+    import ulp_ref as U
+    for op in ("sin", "cos", "exp"):
+        x = U.with_specials(U.sweep(op, "f64", n=n), U.specials("f64"))
+        ref = U.reference(op, x, "f64", use_mp=True)
+        d = dja.distribute(x)
+        out = dja.dmap(op, d)
+        try:
+            got = out.localpart().copy()
+        finally:
+            out.close(); d.close()
+        err = U.ulp_err(got, ref, "f64")
+        fast = fm.fast_range(op, x)
+        w, at = U.worst(err[fast], x[fast])
+        print("map %s f64, %d elements: worst %.4f ulp at %r" % (
+            op, x.size, w, float(at)))
+        assert w <= 1.0 + U.REF_SLACK, (op, w, float(at))
+        assert err[~fast].max() <= 3.0 + U.REF_SLACK, (op, err[~fast].max())
+        assert np.array_equal(kr.bits(got[fast]),
+                              kr.bits(fm.MODEL[op](x[fast]))), op
+
+
 # -------------------------------------------------------------------- gemm
 GEMM_FN = {"f64": "da_gemm_f64", "f32": "da_gemm_f32", "i64": "da_gemm_i64"}
 

@@ -75,6 +75,8 @@ def run_small(dja, lib):
     assert np.array_equal(o.localpart(), x * 2.0 + 1.0)
     s = dja.dmap("abs2", d)
     assert np.array_equal(s.localpart(), x * x)
+    import kernel_checks as kc
+    kc.check_map_ulp(dja)
     for h in (o, s, d, C, dA, dB):
         h.close()
 
