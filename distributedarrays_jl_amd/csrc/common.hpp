@@ -93,6 +93,32 @@ inline size_t dtype_size(int dtype) {
     return 0;
 }
 
+// One dtype switch for a launcher.  ALLOWED is a mask of the DT_* bits the
+// caller accepts; body is a generic lambda called with a dtype_tag<T> of the
+// element type (`using T = typename decltype(tag)::type;`) and launches.
+// It is instantiated for allowed types only, so a launcher emits no kernel
+// for a dtype it refuses.  Returns -3 "<who>: bad dtype %d" for any other
+// dtype, else the status of the launch.
+enum : unsigned { DT_F64 = 1u << DA_F64, DT_F32 = 1u << DA_F32,
+                  DT_I64 = 1u << DA_I64, DT_FLOAT = DT_F64 | DT_F32,
+                  DT_ALL = DT_FLOAT | DT_I64 };
+template <typename T> struct dtype_tag { using type = T; };
+
+template <unsigned ALLOWED, typename L>
+inline int dispatch_dtype(int dtype, const char* who, L body) {
+    if (dtype == DA_F64 && (ALLOWED & DT_F64)) {
+        if constexpr ((ALLOWED & DT_F64) != 0) body(dtype_tag<double>{});
+    } else if (dtype == DA_F32 && (ALLOWED & DT_F32)) {
+        if constexpr ((ALLOWED & DT_F32) != 0) body(dtype_tag<float>{});
+    } else if (dtype == DA_I64 && (ALLOWED & DT_I64)) {
+        if constexpr ((ALLOWED & DT_I64) != 0) body(dtype_tag<int64_t>{});
+    } else {
+        return set_err(-3, "%s: bad dtype %d", who, dtype);
+    }
+    DA_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 int ensure_scratch(size_t bytes);
 int ensure_partials(size_t bytes);
 

@@ -1,5 +1,6 @@
 // kernels_elementwise.hip — fill / philox-rand / map / map2 / fused
-// broadcast / axpby / add / scale for gfx950 (CDNA4).
+// broadcast / axpby / add / scale / cast / transpose / diag for gfx950
+// (CDNA4).
 //
 // These replace the reference's per-worker Base loops on localparts:
 //   map!            /root/reference/src/mapreduce.jl:5-12
@@ -8,9 +9,14 @@
 //   fill!/rand!     /root/reference/src/darray.jl:468-532,822-834
 //   add!/axpy!/rmul!/root/reference/src/linalg.jl:24-76
 //
-// All HBM-bound: grid-stride loops, 16 B/lane vectorized access
-// (double2 / float4 / longlong2), no LDS needed.  This file is compiled
-// with -ffp-contract=off so that a*b+c keeps Julia-Base/numpy bit
+// All HBM-bound, no LDS needed.  Every pointwise kernel is one instance of
+// pointwise_kernel: a grid-stride loop over vectors of W lanes (W = 4 is
+// 32 B/lane for 8-byte types, W = 2 is 16 B, W = 1 scalar) and a scalar
+// tail; the functor passed in owns only the arithmetic of one element (its
+// operator() is force-inlined: left to the inliner, the runtime-op switch
+// becomes a function call).
+// The five rand kernels are rand_kernel over a generator.  This file is
+// compiled with -ffp-contract=off so that a*b+c keeps Julia-Base/numpy bit
 // semantics (separate mul, add); transcendentals use OCML and are
 // parity-tested at 2-3 ulp tolerance.
 #include "common.hpp"
@@ -18,21 +24,28 @@
 #include "mapops.hpp"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
+#include <utility>
 
 namespace da {
 
 constexpr int TPB = 256;
 constexpr int MAXBLOCKS = 8192;   // 1024 workgroups per XCD — fills the chip
 
-static inline bool use_nt() {
-    static int nt = -1;
-    if (nt < 0) {
-        const char* e = getenv("DA_NT");
-        nt = e ? atoi(e) : 0;
-    }
-    return nt == 1;
-}
-
+// Blocks per launcher, as each was last measured.  The formulas disagree
+// with the lane widths on purpose: making them agree changes speed and is
+// not a tidy-up.
+//
+//   launcher            lanes               blocks from
+//   fill                W2, NT gate         n/2 + 1
+//   rand                2 per philox block  n/2 + 1 (uniform f32: 4, n/4 + 1)
+//   map hot/cold/i64    W4|W2 / W2 / W1     n/2 + 1  (W2-sized for all three)
+//   map2 float/i64      W2 / W1             n/2 + 1  (i64: twice the lanes)
+//   map2_scalar         W1                  n
+//   bcast_fma           W4, or W2 + NT gate n/2 + 1  (W2-sized for W4 too)
+//   axpby, add, scale   W4                  n        (scalar-sized)
+//   cast                W1                  n
+//   diag_scale          W1                  m*n
 static inline int nblocks(uint64_t work) {
     uint64_t b = (work + TPB - 1) / TPB;
     if (b > (uint64_t)MAXBLOCKS) b = MAXBLOCKS;
@@ -40,257 +53,259 @@ static inline int nblocks(uint64_t work) {
     return (int)b;
 }
 
-// ------------------------------------------------------------------- fill
-// NT = nontemporal stores on the write-only stream (gfx950 `nt` flag) —
-// A/B-gated via DA_NT; profiles/ record the measured winner.
-template <typename T, bool NT>
-__global__ void fill_kernel(T* __restrict__ p, T v, uint64_t n) {
+// A/B switches, read once per process; profiles/ record the measured
+// winners.
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+// nontemporal stores on write-only streams (gfx950 `nt` flag)
+static bool use_nt() {
+    static const int v = env_int("DA_NT", 0);
+    return v == 1;
+}
+// hot map ops: W4 sin 0.878 ms vs W2 0.946 (and vs same-box hipMemcpy 0.881)
+static bool map_w4() {
+    static const int v = env_int("DA_MAP_W", 4);
+    return v == 4;
+}
+// bcast_fma: W4 1.21 vs W2 1.37 ms on 2^28; the NT kernel exists as W2 only
+static bool bcast_w4() {
+    static const int v = env_int("DA_BC_W", 4);
+    return v == 4 && !use_nt();
+}
+
+// -------------------------------------------------------------- pointwise
+// dst[j] = f(src[j]...), or f(dst[j], src[j]...) when F::reads_dst: the
+// in-place kernels (axpby, add, scale) reach their destination through
+// this one pointer only.  NT: nontemporal vector stores.
+//
+// Caller contract: dst may be exactly one of the sources (map_(op, d, d))
+// — element j is read before it is written and no other thread touches it
+// — but may never partially overlap one.
+template <typename T, int W>
+using vec = T __attribute__((ext_vector_type(W)));
+
+// lane K of the result, from lane K of every operand
+template <int K, typename F, typename... V>
+__device__ __forceinline__ auto lane(const F& f, const V&... v) {
+    return f(v[K]...);
+}
+// all W lanes at dv: one vector per source in v, the old destination vector
+// in front of them for an in-place functor
+template <typename F, typename TD, int... K, typename... V>
+__device__ __forceinline__ vec<TD, sizeof...(K)> lanes(
+        const F& f, const vec<TD, sizeof...(K)>* dv,
+        std::integer_sequence<int, K...>, const V&... v) {
+    if constexpr (F::reads_dst) {
+        const vec<TD, sizeof...(K)> old = *dv;
+        return {lane<K>(f, old, v...)...};
+    } else {
+        return {lane<K>(f, v...)...};
+    }
+}
+
+template <int W, bool NT, typename F, typename TD, typename... TS>
+__global__ void pointwise_kernel(F f, TD* __restrict__ dst, uint64_t n,
+                                 const TS* __restrict__... src) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    // 2 elements per thread via vector store where possible
-    uint64_t nv = n / 2;
-    using V = T __attribute__((ext_vector_type(2)));
-    V vv = {v, v};
-    V* pv = reinterpret_cast<V*>(p);
-    for (uint64_t j = i; j < nv; j += stride) {
-        if (NT) __builtin_nontemporal_store(vv, pv + j);
-        else pv[j] = vv;
+    uint64_t tail = 0;
+    if constexpr (W > 1) {
+        uint64_t nv = n / W;
+        tail = W * nv;
+        vec<TD, W>* dv = reinterpret_cast<vec<TD, W>*>(dst);
+        for (uint64_t j = i; j < nv; j += stride) {
+            const vec<TD, W> r = lanes(
+                f, dv + j, std::make_integer_sequence<int, W>{},
+                reinterpret_cast<const vec<TS, W>*>(src)[j]...);
+            if constexpr (NT) __builtin_nontemporal_store(r, dv + j);
+            else dv[j] = r;
+        }
     }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride) p[j] = v;
+    for (uint64_t j = tail + i; j < n; j += stride) {
+        if constexpr (F::reads_dst) dst[j] = f(dst[j], src[j]...);
+        else dst[j] = f(src[j]...);
+    }
 }
+
+template <int W, bool NT, typename F, typename TD, typename... TS>
+static void stream(int g, hipStream_t s, F f, TD* dst, uint64_t n,
+                   const TS*... src) {
+    hipLaunchKernelGGL((pointwise_kernel<W, NT, F, TD, TS...>), dim3(g),
+                       dim3(TPB), 0, s, f, dst, n, src...);
+}
+
+// float and i64 op tables of mapops.hpp behind one name
+template <typename T>
+__device__ __forceinline__ T map1(int op, T x) {
+    if constexpr (std::is_same<T, int64_t>::value) return apply_map_i64(op, x);
+    else return apply_map<T>(op, x);
+}
+template <typename T>
+__device__ __forceinline__ T map2(int op, T a, T b) {
+    if constexpr (std::is_same<T, int64_t>::value)
+        return apply_map2_i64(op, a, b);
+    else return apply_map2<T>(op, a, b);
+}
+
+// ------------------------------------------------------------------- fill
+template <typename T>
+struct Fill {
+    static constexpr bool reads_dst = false;
+    T v;
+    __device__ __forceinline__ T operator()() const { return v; }
+};
 
 int launch_fill(void* chunk, double v, uint64_t n, int dtype, hipStream_t s) {
     if (n == 0) return 0;
     int g = nblocks(n / 2 + 1);
-    if (use_nt()) {
-        switch (dtype) {
-        case DA_F64:
-            hipLaunchKernelGGL((fill_kernel<double, true>), dim3(g),
-                               dim3(TPB), 0, s, (double*)chunk, v, n); break;
-        case DA_F32:
-            hipLaunchKernelGGL((fill_kernel<float, true>), dim3(g),
-                               dim3(TPB), 0, s, (float*)chunk, (float)v, n);
-            break;
-        case DA_I64:
-            hipLaunchKernelGGL((fill_kernel<int64_t, true>), dim3(g),
-                               dim3(TPB), 0, s, (int64_t*)chunk,
-                               (int64_t)v, n); break;
-        default: return set_err(-3, "da_fill: bad dtype %d", dtype);
-        }
-        DA_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    switch (dtype) {
-    case DA_F64:
-        hipLaunchKernelGGL((fill_kernel<double, false>), dim3(g), dim3(TPB),
-                           0, s, (double*)chunk, v, n); break;
-    case DA_F32:
-        hipLaunchKernelGGL((fill_kernel<float, false>), dim3(g), dim3(TPB),
-                           0, s, (float*)chunk, (float)v, n); break;
-    case DA_I64:
-        hipLaunchKernelGGL((fill_kernel<int64_t, false>), dim3(g), dim3(TPB),
-                           0, s, (int64_t*)chunk, (int64_t)v, n); break;
-    default: return set_err(-3, "da_fill: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_fill", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (use_nt()) stream<2, true>(g, s, Fill<T>{(T)v}, (T*)chunk, n);
+        else stream<2, false>(g, s, Fill<T>{(T)v}, (T*)chunk, n);
+    });
 }
 
 // ------------------------------------------------------------------- rand
-// Element mapping documented in oracle/philox.py (bit-identical contract).
-__global__ void rand_f64_uniform(double* __restrict__ p, uint64_t n,
-                                 uint64_t seed, uint64_t offset) {
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t first_blk = offset >> 1, last_blk = (offset + n - 1) >> 1;
-    for (uint64_t b = first_blk + t; b <= last_blk; b += stride) {
-        u32x4 o = philox4x32_10(b, seed);
-        double v0 = u01_f64(o.v[0], o.v[1]);
-        double v1 = u01_f64(o.v[2], o.v[3]);
-        uint64_t e0 = 2 * b, e1 = 2 * b + 1;
-        if (e0 >= offset && e0 < offset + n) p[e0 - offset] = v0;
-        if (e1 >= offset && e1 < offset + n) p[e1 - offset] = v1;
+// Element mapping documented in oracle/philox.py (bit-identical contract):
+// philox block b yields elements PER*b .. PER*b + PER-1 of the stream, of
+// which this call writes [offset, offset + n).
+// A generator turns one block into PER outputs: prep() does the work they
+// share, elem<J>() makes output J.  J is a template constant, not a loop
+// variable: with both outputs of a normal in one expression the compiler
+// merges the cos and sin argument reductions and runs the large-argument
+// path unconditionally (measured 0.81 vs 0.71 ms per 2^27 f64).
+struct UniformF64 {
+    using T = double;
+    static constexpr int PER = 2;
+    static __device__ __forceinline__ u32x4 prep(const u32x4& o) { return o; }
+    template <int J>
+    static __device__ __forceinline__ T elem(const u32x4& o) {
+        return u01_f64(o.v[2 * J], o.v[2 * J + 1]);
     }
-}
-
-__global__ void rand_f32_uniform(float* __restrict__ p, uint64_t n,
-                                 uint64_t seed, uint64_t offset) {
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t first_blk = offset >> 2, last_blk = (offset + n - 1) >> 2;
-    for (uint64_t b = first_blk + t; b <= last_blk; b += stride) {
-        u32x4 o = philox4x32_10(b, seed);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint64_t e = 4 * b + j;
-            if (e >= offset && e < offset + n) p[e - offset] = u01_f32(o.v[j]);
-        }
+};
+struct UniformF32 {
+    using T = float;
+    static constexpr int PER = 4;
+    static __device__ __forceinline__ u32x4 prep(const u32x4& o) { return o; }
+    template <int J>
+    static __device__ __forceinline__ T elem(const u32x4& o) {
+        return u01_f32(o.v[J]);
     }
-}
-
-__global__ void rand_i64(int64_t* __restrict__ p, uint64_t n,
-                         uint64_t seed, uint64_t offset) {
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t first_blk = offset >> 1, last_blk = (offset + n - 1) >> 1;
-    for (uint64_t b = first_blk + t; b <= last_blk; b += stride) {
-        u32x4 o = philox4x32_10(b, seed);
-        int64_t v0 = (int64_t)(((uint64_t)o.v[1] << 32) | o.v[0]);
-        int64_t v1 = (int64_t)(((uint64_t)o.v[3] << 32) | o.v[2]);
-        uint64_t e0 = 2 * b, e1 = 2 * b + 1;
-        if (e0 >= offset && e0 < offset + n) p[e0 - offset] = v0;
-        if (e1 >= offset && e1 < offset + n) p[e1 - offset] = v1;
+};
+struct RawI64 {
+    using T = int64_t;
+    static constexpr int PER = 2;
+    static __device__ __forceinline__ u32x4 prep(const u32x4& o) { return o; }
+    template <int J>
+    static __device__ __forceinline__ T elem(const u32x4& o) {
+        return (int64_t)(((uint64_t)o.v[2 * J + 1] << 32) | o.v[2 * J]);
     }
-}
-
-__global__ void rand_f64_normal(double* __restrict__ p, uint64_t n,
-                                uint64_t seed, uint64_t offset) {
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t first_blk = offset >> 1, last_blk = (offset + n - 1) >> 1;
-    for (uint64_t b = first_blk + t; b <= last_blk; b += stride) {
-        u32x4 o = philox4x32_10(b, seed);
+};
+template <typename F> struct Polar { F r, th; };   // Box-Muller on one block
+struct NormalF64 {
+    using T = double;
+    static constexpr int PER = 2;
+    static __device__ __forceinline__ Polar<double> prep(const u32x4& o) {
         double u1 = u01_f64(o.v[0], o.v[1]);
         double u2 = u01_f64(o.v[2], o.v[3]);
-        double r = sqrt(-2.0 * log1p(-u1));
-        double th = 2.0 * M_PI * u2;
-        uint64_t e0 = 2 * b, e1 = 2 * b + 1;
-        if (e0 >= offset && e0 < offset + n) p[e0 - offset] = r * cos(th);
-        if (e1 >= offset && e1 < offset + n) p[e1 - offset] = r * sin(th);
+        return {sqrt(-2.0 * log1p(-u1)), 2.0 * M_PI * u2};
     }
-}
-
-__global__ void rand_f32_normal(float* __restrict__ p, uint64_t n,
-                                uint64_t seed, uint64_t offset) {
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t first_blk = offset >> 1, last_blk = (offset + n - 1) >> 1;
-    for (uint64_t b = first_blk + t; b <= last_blk; b += stride) {
-        u32x4 o = philox4x32_10(b, seed);
+    template <int J>
+    static __device__ __forceinline__ T elem(const Polar<double>& p) {
+        if constexpr (J == 0) return p.r * cos(p.th);
+        else return p.r * sin(p.th);
+    }
+};
+struct NormalF32 {
+    using T = float;
+    static constexpr int PER = 2;
+    static __device__ __forceinline__ Polar<float> prep(const u32x4& o) {
         float u1 = u01_f32(o.v[0]);
         float u2 = u01_f32(o.v[1]);
-        float r = sqrtf(-2.0f * log1pf(-u1));
-        float th = 2.0f * (float)M_PI * u2;
-        uint64_t e0 = 2 * b, e1 = 2 * b + 1;
-        if (e0 >= offset && e0 < offset + n) p[e0 - offset] = r * cosf(th);
-        if (e1 >= offset && e1 < offset + n) p[e1 - offset] = r * sinf(th);
+        return {sqrtf(-2.0f * log1pf(-u1)), 2.0f * (float)M_PI * u2};
     }
+    template <int J>
+    static __device__ __forceinline__ T elem(const Polar<float>& p) {
+        if constexpr (J == 0) return p.r * cosf(p.th);
+        else return p.r * sinf(p.th);
+    }
+};
+
+// outputs J... of block b, each stored only if this call covers it
+template <typename G, typename S, int... J>
+__device__ __forceinline__ void rand_store(
+        typename G::T* __restrict__ p, uint64_t n, uint64_t offset,
+        uint64_t b, const S& st, std::integer_sequence<int, J...>) {
+    ((G::PER * b + J >= offset && G::PER * b + J < offset + n
+          ? (void)(p[G::PER * b + J - offset] = G::template elem<J>(st))
+          : (void)0), ...);
+}
+
+template <typename G>
+__global__ void rand_kernel(typename G::T* __restrict__ p, uint64_t n,
+                            uint64_t seed, uint64_t offset) {
+    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t first_blk = offset / G::PER, last_blk = (offset + n - 1) / G::PER;
+    for (uint64_t b = first_blk + t; b <= last_blk; b += stride)
+        rand_store<G>(p, n, offset, b, G::prep(philox4x32_10(b, seed)),
+                      std::make_integer_sequence<int, G::PER>{});
+}
+
+template <typename G>
+static void rand_stream(void* chunk, uint64_t n, uint64_t seed,
+                        uint64_t offset, hipStream_t s) {
+    hipLaunchKernelGGL(rand_kernel<G>, dim3(nblocks(n / G::PER + 1)),
+                       dim3(TPB), 0, s, (typename G::T*)chunk, n, seed,
+                       offset);
 }
 
 int launch_rand(void* chunk, uint64_t n, int dtype, uint64_t seed, int kind,
                 uint64_t offset, hipStream_t s) {
     if (n == 0) return 0;
-    int g = nblocks(n / 2 + 1);
-    if (kind == DA_RAND_UNIFORM) {
-        switch (dtype) {
-        case DA_F64: hipLaunchKernelGGL(rand_f64_uniform, dim3(g), dim3(TPB),
-                        0, s, (double*)chunk, n, seed, offset); break;
-        case DA_F32: hipLaunchKernelGGL(rand_f32_uniform, dim3(nblocks(n/4+1)),
-                        dim3(TPB), 0, s, (float*)chunk, n, seed, offset); break;
-        case DA_I64: hipLaunchKernelGGL(rand_i64, dim3(g), dim3(TPB), 0, s,
-                        (int64_t*)chunk, n, seed, offset); break;
-        default: return set_err(-3, "da_rand: bad dtype %d", dtype);
-        }
-    } else if (kind == DA_RAND_NORMAL) {
-        switch (dtype) {
-        case DA_F64: hipLaunchKernelGGL(rand_f64_normal, dim3(g), dim3(TPB),
-                        0, s, (double*)chunk, n, seed, offset); break;
-        case DA_F32: hipLaunchKernelGGL(rand_f32_normal, dim3(g), dim3(TPB),
-                        0, s, (float*)chunk, n, seed, offset); break;
-        default: return set_err(-3, "da_rand: normal needs float dtype");
-        }
-    } else {
+    if (kind != DA_RAND_UNIFORM && kind != DA_RAND_NORMAL)
         return set_err(-3, "da_rand: bad kind %d", kind);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    const bool normal = kind == DA_RAND_NORMAL;
+    if (normal && dtype != DA_F64 && dtype != DA_F32)
+        return set_err(-3, "da_rand: normal needs float dtype");
+    return dispatch_dtype<DT_ALL>(dtype, "da_rand", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if constexpr (std::is_same<T, double>::value) {
+            if (normal) rand_stream<NormalF64>(chunk, n, seed, offset, s);
+            else rand_stream<UniformF64>(chunk, n, seed, offset, s);
+        } else if constexpr (std::is_same<T, float>::value) {
+            if (normal) rand_stream<NormalF32>(chunk, n, seed, offset, s);
+            else rand_stream<UniformF32>(chunk, n, seed, offset, s);
+        } else {
+            rand_stream<RawI64>(chunk, n, seed, offset, s);
+        }
+    });
 }
 
-template <typename T>
-__global__ void map_kernel(int op, T* __restrict__ dst,
-                           const T* __restrict__ src, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* sv = reinterpret_cast<const V*>(src);
-    V* dv = reinterpret_cast<V*>(dst);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        V r;
-        r.x = apply_map<T>(op, v.x);
-        r.y = apply_map<T>(op, v.y);
-        dv[j] = r;
+// -------------------------------------------------------------------- map
+struct MapOp {                      // op chosen at run time
+    static constexpr bool reads_dst = false;
+    int op;
+    template <typename T>
+    __device__ __forceinline__ T operator()(T x) const {
+        return map1<T>(op, x);
     }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride)
-        dst[j] = apply_map<T>(op, src[j]);
-}
-
-__global__ void map_kernel_i64(int op, int64_t* __restrict__ dst,
-                               const int64_t* __restrict__ src, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride)
-        dst[j] = apply_map_i64(op, src[j]);
-}
+};
 
 // Hot ops get compile-time instantiations: the 63-case runtime switch
 // inflates register pressure (map!(sin) measured 1.08 -> 1.99 ms when
 // the extended op set landed); with OP a template constant the switch
 // folds to one case.
-template <typename T, int OP>
-__global__ void map_fixed_kernel(T* __restrict__ dst,
-                                 const T* __restrict__ src, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* sv = reinterpret_cast<const V*>(src);
-    V* dv = reinterpret_cast<V*>(dst);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        V r;
-        r.x = apply_map<T>(OP, v.x);
-        r.y = apply_map<T>(OP, v.y);
-        dv[j] = r;
+template <int OP>
+struct MapFixed {
+    static constexpr bool reads_dst = false;
+    template <typename T>
+    __device__ __forceinline__ T operator()(T x) const {
+        return apply_map<T>(OP, x);
     }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride)
-        dst[j] = apply_map<T>(OP, src[j]);
-}
-
-// 32 B/lane variant (double4): more memory-level parallelism per
-// wave iteration — A/B-gated via DA_MAP_W=4 against the 16 B default.
-template <typename T, int OP>
-__global__ void map_fixed_kernel_w4(T* __restrict__ dst,
-                                    const T* __restrict__ src, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(4)));
-    uint64_t nv = n / 4;
-    const V* sv = reinterpret_cast<const V*>(src);
-    V* dv = reinterpret_cast<V*>(dst);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V v = sv[j];
-        V r;
-        r.x = apply_map<T>(OP, v.x);
-        r.y = apply_map<T>(OP, v.y);
-        r.z = apply_map<T>(OP, v.z);
-        r.w = apply_map<T>(OP, v.w);
-        dv[j] = r;
-    }
-    for (uint64_t j = 4 * nv + i; j < n; j += stride)
-        dst[j] = apply_map<T>(OP, src[j]);
-}
-
-static inline int map_width() {
-    static int w = -1;
-    if (w < 0) {
-        const char* e = getenv("DA_MAP_W");
-        w = e ? atoi(e) : 4;   // measured: W4 sin 0.878 ms vs W2 0.946
-                               // (and vs same-box hipMemcpy 0.881)
-    }
-    return w;
-}
+};
 
 #define DA_HOT_OPS(X)                                                   \
     X(DA_OP_IDENTITY) X(DA_OP_NEG) X(DA_OP_ABS) X(DA_OP_ABS2)           \
@@ -298,23 +313,21 @@ static inline int map_width() {
     X(DA_OP_SIN) X(DA_OP_COS) X(DA_OP_TAN) X(DA_OP_TANH)                \
     X(DA_OP_FLOOR) X(DA_OP_SIGN) X(DA_OP_LOG1P) X(DA_OP_EXPM1)
 
+// float map: hot ops at W4 (or W2), every other op through the runtime
+// switch at W2
 template <typename T>
-static bool launch_map_hot(int opcode, T* dst, const T* src, uint64_t n,
-                           int g, hipStream_t s) {
+static void map_float(int opcode, T* dst, const T* src, uint64_t n, int g,
+                      hipStream_t s) {
     switch (opcode) {
 #define DA_CASE(OPC)                                                    \
     case OPC:                                                           \
-        if (map_width() == 4)                                           \
-            hipLaunchKernelGGL((map_fixed_kernel_w4<T, OPC>), dim3(g),  \
-                               dim3(TPB), 0, s, dst, src, n);           \
-        else                                                            \
-            hipLaunchKernelGGL((map_fixed_kernel<T, OPC>), dim3(g),     \
-                               dim3(TPB), 0, s, dst, src, n);           \
-        return true;
+        if (map_w4()) stream<4, false>(g, s, MapFixed<OPC>{}, dst, n, src); \
+        else stream<2, false>(g, s, MapFixed<OPC>{}, dst, n, src);      \
+        return;
     DA_HOT_OPS(DA_CASE)
 #undef DA_CASE
     }
-    return false;
+    stream<2, false>(g, s, MapOp{opcode}, dst, n, src);
 }
 
 int launch_map(int opcode, void* dst, const void* src, uint64_t n, int dtype,
@@ -322,64 +335,30 @@ int launch_map(int opcode, void* dst, const void* src, uint64_t n, int dtype,
     if (n == 0) return 0;
     if (opcode < 0 || opcode >= DA_OP__N)
         return set_err(-3, "da_map: bad opcode %d", opcode);
+    if (dtype == DA_I64 &&
+        !(opcode == DA_OP_IDENTITY || opcode == DA_OP_NEG ||
+          opcode == DA_OP_ABS || opcode == DA_OP_ABS2 ||
+          opcode == DA_OP_SIGN))
+        return set_err(-3, "da_map: opcode %d invalid for i64", opcode);
     int g = nblocks(n / 2 + 1);
-    switch (dtype) {
-    case DA_F64:
-        if (launch_map_hot<double>(opcode, (double*)dst,
-                                   (const double*)src, n, g, s))
-            break;
-        hipLaunchKernelGGL(map_kernel<double>, dim3(g), dim3(TPB),
-                    0, s, opcode, (double*)dst, (const double*)src, n); break;
-    case DA_F32:
-        if (launch_map_hot<float>(opcode, (float*)dst,
-                                  (const float*)src, n, g, s))
-            break;
-        hipLaunchKernelGGL(map_kernel<float>, dim3(g), dim3(TPB),
-                    0, s, opcode, (float*)dst, (const float*)src, n); break;
-    case DA_I64:
-        if (!(opcode == DA_OP_IDENTITY || opcode == DA_OP_NEG ||
-              opcode == DA_OP_ABS || opcode == DA_OP_ABS2 ||
-              opcode == DA_OP_SIGN))
-            return set_err(-3, "da_map: opcode %d invalid for i64", opcode);
-        hipLaunchKernelGGL(map_kernel_i64, dim3(g), dim3(TPB), 0, s,
-                           opcode, (int64_t*)dst, (const int64_t*)src, n);
-        break;
-    default: return set_err(-3, "da_map: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_map", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if constexpr (std::is_same<T, int64_t>::value)
+            stream<1, false>(g, s, MapOp{opcode}, (T*)dst, n, (const T*)src);
+        else
+            map_float<T>(opcode, (T*)dst, (const T*)src, n, g, s);
+    });
 }
 
 // ------------------------------------------------------------------- map2
-template <typename T>
-__global__ void map2_kernel(int op, T* __restrict__ dst,
-                            const T* __restrict__ a,
-                            const T* __restrict__ b, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* av = reinterpret_cast<const V*>(a);
-    const V* bv = reinterpret_cast<const V*>(b);
-    V* dv = reinterpret_cast<V*>(dst);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V x = av[j], y = bv[j], r;
-        r.x = apply_map2<T>(op, x.x, y.x);
-        r.y = apply_map2<T>(op, x.y, y.y);
-        dv[j] = r;
+struct Map2Op {
+    static constexpr bool reads_dst = false;
+    int op;
+    template <typename T>
+    __device__ __forceinline__ T operator()(T a, T b) const {
+        return map2<T>(op, a, b);
     }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride)
-        dst[j] = apply_map2<T>(op, a[j], b[j]);
-}
-
-__global__ void map2_kernel_i64(int op, int64_t* __restrict__ dst,
-                                const int64_t* __restrict__ a,
-                                const int64_t* __restrict__ b, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride)
-        dst[j] = apply_map2_i64(op, a[j], b[j]);
-}
+};
 
 int launch_map2(int opcode, void* dst, const void* a, const void* b,
                 uint64_t n, int dtype, hipStream_t s) {
@@ -387,45 +366,27 @@ int launch_map2(int opcode, void* dst, const void* a, const void* b,
     if (opcode < 0 || opcode >= DA_OP2__N)
         return set_err(-3, "da_map2: bad opcode %d", opcode);
     int g = nblocks(n / 2 + 1);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(map2_kernel<double>, dim3(g), dim3(TPB),
-                    0, s, opcode, (double*)dst, (const double*)a,
-                    (const double*)b, n); break;
-    case DA_F32: hipLaunchKernelGGL(map2_kernel<float>, dim3(g), dim3(TPB),
-                    0, s, opcode, (float*)dst, (const float*)a,
-                    (const float*)b, n); break;
-    case DA_I64: hipLaunchKernelGGL(map2_kernel_i64, dim3(g), dim3(TPB), 0, s,
-                    opcode, (int64_t*)dst, (const int64_t*)a,
-                    (const int64_t*)b, n); break;
-    default: return set_err(-3, "da_map2: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_map2", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr int W = std::is_same<T, int64_t>::value ? 1 : 2;
+        stream<W, false>(g, s, Map2Op{opcode}, (T*)dst, n, (const T*)a,
+                         (const T*)b);
+    });
 }
 
 // scalar-broadcast forms: D .= f.(src, c) / f.(c, src) (e.g. D .+ 1,
 // the cfg-1 plumbing op; Base broadcast with a scalar argument —
 // broadcast.jl:124-133 treats singletons as local, no distribution)
 template <typename T>
-__global__ void map2s_kernel(int op, T* __restrict__ dst,
-                             const T* __restrict__ a, T c, int rev,
-                             uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride)
-        dst[j] = rev ? apply_map2<T>(op, c, a[j])
-                     : apply_map2<T>(op, a[j], c);
-}
-
-__global__ void map2s_kernel_i64(int op, int64_t* __restrict__ dst,
-                                 const int64_t* __restrict__ a, int64_t c,
-                                 int rev, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride)
-        dst[j] = rev ? apply_map2_i64(op, c, a[j])
-                     : apply_map2_i64(op, a[j], c);
-}
+struct Map2Scalar {
+    static constexpr bool reads_dst = false;
+    int op;
+    T c;
+    int rev;
+    __device__ __forceinline__ T operator()(T a) const {
+        return rev ? map2<T>(op, c, a) : map2<T>(op, a, c);
+    }
+};
 
 int launch_map2_scalar(int opcode, void* dst, const void* src, double c,
                        int rev, uint64_t n, int dtype, hipStream_t s) {
@@ -433,20 +394,11 @@ int launch_map2_scalar(int opcode, void* dst, const void* src, double c,
     if (opcode < 0 || opcode >= DA_OP2__N)
         return set_err(-3, "da_map2_scalar: bad opcode %d", opcode);
     int g = nblocks(n);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(map2s_kernel<double>, dim3(g),
-                    dim3(TPB), 0, s, opcode, (double*)dst,
-                    (const double*)src, c, rev, n); break;
-    case DA_F32: hipLaunchKernelGGL(map2s_kernel<float>, dim3(g),
-                    dim3(TPB), 0, s, opcode, (float*)dst,
-                    (const float*)src, (float)c, rev, n); break;
-    case DA_I64: hipLaunchKernelGGL(map2s_kernel_i64, dim3(g), dim3(TPB),
-                    0, s, opcode, (int64_t*)dst, (const int64_t*)src,
-                    (int64_t)c, rev, n); break;
-    default: return set_err(-3, "da_map2_scalar: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_map2_scalar", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        stream<1, false>(g, s, Map2Scalar<T>{opcode, (T)c, rev}, (T*)dst, n,
+                         (const T*)src);
+    });
 }
 
 
@@ -479,17 +431,11 @@ int launch_transpose(void* dst, const void* src, uint64_t m, uint64_t n,
                      int dtype, hipStream_t s) {
     if (m == 0 || n == 0) return 0;
     dim3 t(32, 8), g((m + 31) / 32, (n + 31) / 32);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(transpose_kernel<double>, g, t, 0, s,
-                    (double*)dst, (const double*)src, m, n); break;
-    case DA_F32: hipLaunchKernelGGL(transpose_kernel<float>, g, t, 0, s,
-                    (float*)dst, (const float*)src, m, n); break;
-    case DA_I64: hipLaunchKernelGGL(transpose_kernel<int64_t>, g, t, 0, s,
-                    (int64_t*)dst, (const int64_t*)src, m, n); break;
-    default: return set_err(-3, "da_transpose: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_transpose", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(transpose_kernel<T>, g, t, 0, s, (T*)dst,
+                           (const T*)src, m, n);
+    });
 }
 
 // Diagonal scaling: side=0 rows (lmul!(Diagonal(d), A), linalg.jl:169-177),
@@ -510,236 +456,97 @@ int launch_diag_scale(void* a, uint64_t m, uint64_t n, const void* diag,
                       int side, int dtype, hipStream_t s) {
     if (m == 0 || n == 0) return 0;
     int g = nblocks(m * n);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(diag_scale_kernel<double>, dim3(g),
-                    dim3(TPB), 0, s, (double*)a, m, n,
-                    (const double*)diag, side); break;
-    case DA_F32: hipLaunchKernelGGL(diag_scale_kernel<float>, dim3(g),
-                    dim3(TPB), 0, s, (float*)a, m, n,
-                    (const float*)diag, side); break;
-    default: return set_err(-3, "da_diag_scale: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_FLOAT>(dtype, "da_diag_scale", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(diag_scale_kernel<T>, dim3(g), dim3(TPB), 0, s,
+                           (T*)a, m, n, (const T*)diag, side);
+    });
 }
 
 // ------------------------------------------- fused broadcast & BLAS-1 like
 template <typename T>
-__global__ void bcast_fma_kernel_w4(T* __restrict__ d,
-                                    const T* __restrict__ a,
-                                    const T* __restrict__ b, T c,
-                                    uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(4)));
-    uint64_t nv = n / 4;
-    const V* av = reinterpret_cast<const V*>(a);
-    const V* bv = reinterpret_cast<const V*>(b);
-    V* dv = reinterpret_cast<V*>(d);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V x = av[j], y = bv[j], r;
-        r.x = x.x * y.x + c;   // -ffp-contract=off (Julia Base)
-        r.y = x.y * y.y + c;
-        r.z = x.z * y.z + c;
-        r.w = x.w * y.w + c;
-        dv[j] = r;
+struct MulAdd {                     // d = a * b + c
+    static constexpr bool reads_dst = false;
+    T c;
+    // -ffp-contract=off: mul then add (Julia Base)
+    __device__ __forceinline__ T operator()(T a, T b) const {
+        return a * b + c;
     }
-    for (uint64_t j = 4 * nv + i; j < n; j += stride) d[j] = a[j] * b[j] + c;
-}
-
-static inline int bc_width() {
-    static int w = -1;
-    if (w < 0) {
-        const char* e = getenv("DA_BC_W");
-        w = e ? atoi(e) : 4;   // measured 1.21 vs 1.37 ms on 2^28
-    }
-    return w;
-}
-
-template <typename T, bool NT>
-__global__ void bcast_fma_kernel(T* __restrict__ d, const T* __restrict__ a,
-                                 const T* __restrict__ b, T c, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(2)));
-    uint64_t nv = n / 2;
-    const V* av = reinterpret_cast<const V*>(a);
-    const V* bv = reinterpret_cast<const V*>(b);
-    V* dv = reinterpret_cast<V*>(d);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V x = av[j], y = bv[j], r;
-        r.x = x.x * y.x + c;   // -ffp-contract=off: mul then add (Julia Base)
-        r.y = x.y * y.y + c;
-        if (NT) __builtin_nontemporal_store(r, dv + j);
-        else dv[j] = r;
-    }
-    for (uint64_t j = 2 * nv + i; j < n; j += stride) d[j] = a[j] * b[j] + c;
-}
+};
 
 int launch_bcast_fma(void* d, const void* a, const void* b, double c,
                      uint64_t n, int dtype, hipStream_t s) {
     if (n == 0) return 0;
     int g = nblocks(n / 2 + 1);
-    if (bc_width() == 4 && !use_nt()) {
-        switch (dtype) {
-        case DA_F64: hipLaunchKernelGGL((bcast_fma_kernel_w4<double>),
-                        dim3(g), dim3(TPB), 0, s, (double*)d,
-                        (const double*)a, (const double*)b, c, n); break;
-        case DA_F32: hipLaunchKernelGGL((bcast_fma_kernel_w4<float>),
-                        dim3(g), dim3(TPB), 0, s, (float*)d,
-                        (const float*)a, (const float*)b, (float)c, n);
-            break;
-        default: return set_err(-3, "da_bcast_fma: bad dtype %d", dtype);
-        }
-        DA_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    if (use_nt()) {
-        switch (dtype) {
-        case DA_F64: hipLaunchKernelGGL((bcast_fma_kernel<double, true>),
-                        dim3(g), dim3(TPB), 0, s, (double*)d,
-                        (const double*)a, (const double*)b, c, n); break;
-        case DA_F32: hipLaunchKernelGGL((bcast_fma_kernel<float, true>),
-                        dim3(g), dim3(TPB), 0, s, (float*)d,
-                        (const float*)a, (const float*)b, (float)c, n);
-            break;
-        default: return set_err(-3, "da_bcast_fma: bad dtype %d", dtype);
-        }
-        DA_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL((bcast_fma_kernel<double, false>),
-                    dim3(g), dim3(TPB), 0, s, (double*)d, (const double*)a,
-                    (const double*)b, c, n); break;
-    case DA_F32: hipLaunchKernelGGL((bcast_fma_kernel<float, false>),
-                    dim3(g), dim3(TPB), 0, s, (float*)d, (const float*)a,
-                    (const float*)b, (float)c, n); break;
-    default: return set_err(-3, "da_bcast_fma: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_FLOAT>(dtype, "da_bcast_fma", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        MulAdd<T> f{(T)c};
+        T* dp = (T*)d;
+        const T *ap = (const T*)a, *bp = (const T*)b;
+        if (bcast_w4()) stream<4, false>(g, s, f, dp, n, ap, bp);
+        else if (use_nt()) stream<2, true>(g, s, f, dp, n, ap, bp);
+        else stream<2, false>(g, s, f, dp, n, ap, bp);
+    });
 }
 
 template <typename T>
-__global__ void axpby_kernel(T* __restrict__ y, const T* __restrict__ x,
-                             T alpha, T beta, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(4)));
-    uint64_t nv = n / 4;
-    const V* xv = reinterpret_cast<const V*>(x);
-    V* yv = reinterpret_cast<V*>(y);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V a = xv[j], b = yv[j], r;
-        r.x = alpha * a.x + beta * b.x;
-        r.y = alpha * a.y + beta * b.y;
-        r.z = alpha * a.z + beta * b.z;
-        r.w = alpha * a.w + beta * b.w;
-        yv[j] = r;
+struct Axpby {                      // y = alpha * x + beta * y
+    static constexpr bool reads_dst = true;
+    T alpha, beta;
+    __device__ __forceinline__ T operator()(T y, T x) const {
+        return alpha * x + beta * y;
     }
-    for (uint64_t j = 4 * nv + i; j < n; j += stride)
-        y[j] = alpha * x[j] + beta * y[j];
-}
+};
 
 int launch_axpby(void* y, const void* x, double alpha, double beta,
                  uint64_t n, int dtype, hipStream_t s) {
     if (n == 0) return 0;
     int g = nblocks(n);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(axpby_kernel<double>, dim3(g), dim3(TPB),
-                    0, s, (double*)y, (const double*)x, alpha, beta, n); break;
-    case DA_F32: hipLaunchKernelGGL(axpby_kernel<float>, dim3(g), dim3(TPB),
-                    0, s, (float*)y, (const float*)x, (float)alpha,
-                    (float)beta, n); break;
-    default: return set_err(-3, "da_axpby: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_FLOAT>(dtype, "da_axpby", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        stream<4, false>(g, s, Axpby<T>{(T)alpha, (T)beta}, (T*)y, n,
+                         (const T*)x);
+    });
 }
 
 // add! (linalg.jl:62-76): scale==1 adds without multiplying, matching the
 // reference's fast path numerics exactly.
 template <typename T>
-__global__ void add_kernel(T* __restrict__ d, const T* __restrict__ s_,
-                           T scale, int unit, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(4)));
-    uint64_t nv = n / 4;
-    const V* sv = reinterpret_cast<const V*>(s_);
-    V* dv = reinterpret_cast<V*>(d);
-    if (unit) {
-        for (uint64_t j = i; j < nv; j += stride) {
-            V a = dv[j], b = sv[j], r;
-            r.x = a.x + b.x; r.y = a.y + b.y;
-            r.z = a.z + b.z; r.w = a.w + b.w;
-            dv[j] = r;
-        }
-        for (uint64_t j = 4 * nv + i; j < n; j += stride)
-            d[j] = d[j] + s_[j];
-    } else {
-        for (uint64_t j = i; j < nv; j += stride) {
-            V a = dv[j], b = sv[j], r;
-            r.x = a.x + scale * b.x; r.y = a.y + scale * b.y;
-            r.z = a.z + scale * b.z; r.w = a.w + scale * b.w;
-            dv[j] = r;
-        }
-        for (uint64_t j = 4 * nv + i; j < n; j += stride)
-            d[j] = d[j] + scale * s_[j];
+struct Add {
+    static constexpr bool reads_dst = true;
+    T scale;
+    int unit;
+    __device__ __forceinline__ T operator()(T d, T s_) const {
+        return unit ? d + s_ : d + scale * s_;
     }
-}
+};
 
 int launch_add(void* dest, const void* src, double scale, uint64_t n,
                int dtype, hipStream_t s) {
     if (n == 0) return 0;
     int g = nblocks(n);
     int unit = (scale == 1.0);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(add_kernel<double>, dim3(g), dim3(TPB),
-                    0, s, (double*)dest, (const double*)src, scale, unit, n);
-                 break;
-    case DA_F32: hipLaunchKernelGGL(add_kernel<float>, dim3(g), dim3(TPB),
-                    0, s, (float*)dest, (const float*)src, (float)scale,
-                    unit, n); break;
-    case DA_I64: hipLaunchKernelGGL(add_kernel<int64_t>, dim3(g), dim3(TPB),
-                    0, s, (int64_t*)dest, (const int64_t*)src,
-                    (int64_t)scale, unit, n); break;
-    default: return set_err(-3, "da_add: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_add", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        stream<4, false>(g, s, Add<T>{(T)scale, unit}, (T*)dest, n,
+                         (const T*)src);
+    });
 }
 
 template <typename T>
-__global__ void scale_kernel(T* __restrict__ a, T v, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    using V = T __attribute__((ext_vector_type(4)));
-    uint64_t nv = n / 4;
-    V* av = reinterpret_cast<V*>(a);
-    for (uint64_t j = i; j < nv; j += stride) {
-        V x = av[j];
-        x.x *= v; x.y *= v; x.z *= v; x.w *= v;
-        av[j] = x;
-    }
-    for (uint64_t j = 4 * nv + i; j < n; j += stride) a[j] = a[j] * v;
-}
+struct Scale {
+    static constexpr bool reads_dst = true;
+    T v;
+    __device__ __forceinline__ T operator()(T a) const { return a * v; }
+};
 
 int launch_scale(void* a, double s_, uint64_t n, int dtype, hipStream_t s) {
     if (n == 0) return 0;
     int g = nblocks(n);
-    switch (dtype) {
-    case DA_F64: hipLaunchKernelGGL(scale_kernel<double>, dim3(g), dim3(TPB),
-                    0, s, (double*)a, s_, n); break;
-    case DA_F32: hipLaunchKernelGGL(scale_kernel<float>, dim3(g), dim3(TPB),
-                    0, s, (float*)a, (float)s_, n); break;
-    case DA_I64: hipLaunchKernelGGL(scale_kernel<int64_t>, dim3(g), dim3(TPB),
-                    0, s, (int64_t*)a, (int64_t)s_, n); break;
-    default: return set_err(-3, "da_scale: bad dtype %d", dtype);
-    }
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dispatch_dtype<DT_ALL>(dtype, "da_scale", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        stream<4, false>(g, s, Scale<T>{(T)s_}, (T*)a, n);
+    });
 }
 
 
@@ -747,56 +554,42 @@ int launch_scale(void* a, double s_, uint64_t n, int dtype, hipStream_t s) {
 // dtype conversion (the DArray{T2}(D) / convert family): dst[i] =
 // (TD)src[i].  float->i64 rounds half-even (Julia round(Int, x)); the
 // strict InexactError convert is a host-side concern.
-template <typename TD, typename TS>
-__global__ void cast_kernel(TD* __restrict__ dst,
-                            const TS* __restrict__ src, uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride) dst[j] = (TD)src[j];
-}
-
-template <>
-__global__ void cast_kernel<int64_t, double>(int64_t* __restrict__ dst,
-                                             const double* __restrict__ src,
-                                             uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride)
-        dst[j] = (int64_t)rint(src[j]);
-}
-
-template <>
-__global__ void cast_kernel<int64_t, float>(int64_t* __restrict__ dst,
-                                            const float* __restrict__ src,
-                                            uint64_t n) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = i; j < n; j += stride)
-        dst[j] = (int64_t)rintf(src[j]);
-}
+template <typename TD>
+struct Cast {
+    static constexpr bool reads_dst = false;
+    template <typename TS>
+    __device__ __forceinline__ TD operator()(TS x) const {
+        if constexpr (std::is_same<TD, int64_t>::value) {
+            if constexpr (std::is_same<TS, float>::value)
+                return (TD)rintf(x);
+            else return (TD)rint(x);
+        } else {
+            return (TD)x;
+        }
+    }
+};
 
 int launch_cast(void* dst, int dst_dtype, const void* src, int src_dtype,
                 uint64_t n, hipStream_t s) {
     if (n == 0) return 0;
     if (dst_dtype == src_dtype)
         return set_err(-3, "da_cast: same dtype (use da_d2d)");
+    if (!dtype_size(dst_dtype) || !dtype_size(src_dtype))
+        return set_err(-3, "da_cast: bad dtypes %d<-%d", dst_dtype,
+                       src_dtype);
     int g = nblocks(n);
-#define DA_CAST(TD, TS) \
-    hipLaunchKernelGGL((cast_kernel<TD, TS>), dim3(g), dim3(TPB), 0, s, \
-                       (TD*)dst, (const TS*)src, n)
-    switch (dst_dtype * 4 + src_dtype) {
-    case DA_F64 * 4 + DA_F32: DA_CAST(double, float); break;
-    case DA_F64 * 4 + DA_I64: DA_CAST(double, int64_t); break;
-    case DA_F32 * 4 + DA_F64: DA_CAST(float, double); break;
-    case DA_F32 * 4 + DA_I64: DA_CAST(float, int64_t); break;
-    case DA_I64 * 4 + DA_F64: DA_CAST(int64_t, double); break;
-    case DA_I64 * 4 + DA_F32: DA_CAST(int64_t, float); break;
-    default: return set_err(-3, "da_cast: bad dtypes %d<-%d",
-                            dst_dtype, src_dtype);
-    }
-#undef DA_CAST
-    DA_CHECK_HIP(hipGetLastError());
-    return 0;
+    // both dtypes are valid here; the inner dispatch reports the launch
+    int rc = 0;
+    dispatch_dtype<DT_ALL>(dst_dtype, "da_cast", [&](auto dtag) {
+        using TD = typename decltype(dtag)::type;
+        rc = dispatch_dtype<DT_ALL>(src_dtype, "da_cast", [&](auto stag) {
+            using TS = typename decltype(stag)::type;
+            if constexpr (!std::is_same<TD, TS>::value)
+                stream<1, false>(g, s, Cast<TD>{}, (TD*)dst, n,
+                                 (const TS*)src);
+        });
+    });
+    return rc;
 }
 
 } // namespace da

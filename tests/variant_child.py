@@ -77,6 +77,9 @@ def run_small(dja, lib):
     assert np.array_equal(s.localpart(), x * x)
     import kernel_checks as kc
     kc.check_map_ulp(dja)
+    # every elementwise launcher at its edges: under DA_NT=1, DA_MAP_W=2
+    # and DA_BC_W=2 these are the vector-of-2 and non-temporal kernels
+    kc.check_elementwise_edges(dja, kc.EDGE_SIZES, kc.EDGE_WRAP)
     for h in (o, s, d, C, dA, dB):
         h.close()
 
